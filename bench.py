@@ -16,6 +16,10 @@ contraction on v_mfma_f32_32x32x2_f32.  The faster split-bf16 product mode (oper
 product: inside the north-star tolerances but narrower than fp32) and the fp32-faithful bf16x6 emulation (exact
 three-way operand split, 6 MFMA per product) are timed in the same run and reported under `split_bf16_mode` /
 `fp32_emulated_bf16x6_mode`; the north-star's other sizes under `sweep`; the CPU oracle under `cpu_baseline`.
+
+`--dump-outputs DIR` writes what the headline mode's last timed step handed back (the mel batch and, on rank 0, the
+waveforms) as DIR/mel.npy and DIR/wave.npy in float32, so that two builds can be compared output for output: inputs and
+weights are seeded, identical from run to run.  Above 60 MB in all, each array is replaced by a fixed seeded sample.
 """
 import argparse
 import glob
@@ -283,6 +287,28 @@ def op_bytes(kw):
     return rd + out_b
 
 
+DUMP_BYTES = 60 * 10**6  # --dump-outputs: under 64 MB with the .npy headers
+
+
+def dump_outputs(d, arrays):
+    """write each array as d/<name>.npy in float32; if together they exceed DUMP_BYTES, each is replaced by the same
+    seeded sample of its flattened elements (its share of the budget, positions in ascending order)"""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items() if v is not None}
+    total = sum(v.nbytes for v in arrays.values())
+    info = {}
+    for k, v in sorted(arrays.items()):
+        rec = {"shape": list(v.shape), "dtype": "float32"}
+        if total > DUMP_BYTES:
+            n = max(1, int(v.size * DUMP_BYTES // total))
+            idx = np.sort(np.random.default_rng(0).choice(v.size, size=n, replace=False))
+            v = v.reshape(-1)[idx]
+            rec["sampled"] = {"elements": int(n), "of": int(arrays[k].size), "seed": 0}
+        np.save(os.path.join(d, k + ".npy"), v)
+        info[k] = rec
+    return {"dir": d, "arrays": info}
+
+
 def main():
     global B_PER_GPU, T_SRC, T_REF, N_EULER
     ap = argparse.ArgumentParser()
@@ -304,10 +330,13 @@ def main():
     ap.add_argument("--ref-frames", type=int, default=T_REF, help="prompt frames per utterance")
     ap.add_argument("--batch", type=int, default=B_PER_GPU, help="utterances per GPU")
     ap.add_argument("--euler", type=int, default=N_EULER, help="Euler ODE steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the headline mode's last timed "
+                    "step returned (mel, waveform) to DIR/<name>.npy in float32, under 64 MB in all")
     args = ap.parse_args()
     B_PER_GPU, T_SRC, T_REF, N_EULER = args.batch, args.frames, args.ref_frames, args.euler
     modes = [m for m in args.modes.split(",") if m]
     assert modes and all(m in DTYPE for m in modes), f"--modes takes {sorted(DTYPE)}"
+    assert args.steps >= 1 and args.warmup >= 0, "--steps >= 1, --warmup >= 0"
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -332,25 +361,29 @@ def main():
     if args.graphs is not None:
         ops.set_graphs(bool(args.graphs))
     gather_ev = []  # (start, end) HIP events around the waveform gather of the timed steps
+    last = {}  # the outputs of the last timed step (--dump-outputs), as the caller of the hot path receives them
 
     def make_step(B, T, T_ref, n, seed):
         d = synth_inputs(B, T, T_ref=T_ref, seed=seed)
         g = {k: (v.to(dev) if v.is_floating_point() else v) for k, v in d.items()}
 
-        def step(timed=False):
+        def step(timed=False, keep=False):
             mel = model.inference(g["x"], g["lengths"], g["midi"], g["lft"], g["ref_x"], g["ref_lengths"],
                                   g["ref_logmel"], g["ref_midi"], g["ref_lft"], n_timesteps=n, noise=g["z"])
             wave = voc.decode_batch(mel if mel.dim() == 3 else mel.unsqueeze(0))  # inference() squeezes B == 1
             if not use_dist:
-                return wave
-            if timed:
+                out = wave
+            elif timed:
                 s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 s.record()
                 out = gather_waveforms(wave, dst=0, uniform=True, always_collective=True)
                 e.record()
                 gather_ev.append((s, e))
-                return out
-            return gather_waveforms(wave, dst=0, uniform=True, always_collective=True)
+            else:
+                out = gather_waveforms(wave, dst=0, uniform=True, always_collective=True)
+            if keep:  # references only: copied to the host after the timed region
+                last["mel"], last["wave"] = mel, out
+            return out
 
         return step
 
@@ -375,12 +408,18 @@ def main():
         prof = []
         del gather_ev[:]
         t0 = time.perf_counter()
+        keep = args.dump_outputs is not None and precision == modes[0]
         for i in range(args.steps):
             ops.PROFILE = prof if i == 0 else None
-            step(timed=True)
+            step(timed=True, keep=keep and i == args.steps - 1)
         ops.PROFILE = None
         sync()
         elapsed = local_elapsed = time.perf_counter() - t0
+        if keep:  # before any other run can reuse the buffers (plans replayed as hipGraphs own their outputs)
+            if use_dist:  # rank 0 holds (per-rank waveforms, lengths), the other ranks None
+                last["wave"] = None if last["wave"] is None else torch.cat(last["wave"][0])
+            for k in list(last):
+                last[k] = None if last[k] is None else last[k].detach().float().cpu().numpy()
         extra = {}
         if use_dist:
             t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -426,6 +465,7 @@ def main():
 
     results = {m: timed(m) for m in modes}
     head = results[modes[0]]
+    dumped = dump_outputs(args.dump_outputs, last) if args.dump_outputs is not None and rank == 0 else None
 
     def mixed_attention():
         """a secondary key: exact-fp32 convs / linears with Q K^T and P V on the bf16 matrix cores (split-bf16, fp32
@@ -504,6 +544,8 @@ def main():
                    else "narrower than the reference's fp32 (split-bf16 operands)", "build": build_id()},
         "roofline": head["roofline"],
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     for k in ("per_rank_ms_per_step", "rank0_gather_ms_per_step", "world_size_seen", "backend",
               "gather_bytes_per_rank"):
         if k in head:

@@ -1,8 +1,10 @@
 """serenade-decode mirror (CPU, through the C-ABI emulator): command line, file formats, outputs; and the
 F0 helpers of the decode loop against hand-computed values (reference: serenade/bin/ssc_decode.py:32-154,190-455)."""
+import contextlib
 import json
 import os
 import wave as wavmod
+from unittest import mock
 
 import numpy as np
 import pytest
@@ -46,6 +48,13 @@ def test_f0_helpers_known_answers():
     assert np.allclose(out[[1, 2]], 220.0 * 2 ** (-5 / 12))
 
 
+@contextlib.contextmanager
+def _emulated():
+    """the C-ABI emulator on the CPU: the CLI picks cuda:0 whenever a GPU is visible, so hide it, as on a CPU box"""
+    with _emulator.installed(), mock.patch.object(torch.cuda, "is_available", return_value=False):
+        yield
+
+
 def _feats(rng, T):
     return dict(wave=(0.1 * rng.standard_normal(T * 240)).astype(np.float32),
                 hubert=rng.standard_normal((T, 32)).astype(np.float32),
@@ -59,7 +68,6 @@ def _feats(rng, T):
 def _cli_case(tmp_path, on_gpu):
     """Build a tiny dump / checkpoint / vocoder / stats tree, run the CLI on it (through the C-ABI emulator on the
     CPU, or the real library on the GPU) and check files, formats and values against the oracle."""
-    import contextlib
     from joblib import dump
     from sklearn.preprocessing import MinMaxScaler, StandardScaler
     rng = np.random.default_rng(0)
@@ -90,7 +98,7 @@ def _cli_case(tmp_path, on_gpu):
                    open(exp / "config.yml", "w"))
     json.dump({"Breathy": str(tmp_path / "ref" / "breathy.npz")}, open(tmp_path / "refs.json", "w"))
 
-    with (contextlib.nullcontext() if on_gpu else _emulator.installed()):
+    with (contextlib.nullcontext() if on_gpu else _emulated()):
         torch.manual_seed(123)
         ssc_decode.main(["--dumpdir", str(dumpdir), "--stats", str(tmp_path / "stats.joblib"), "--ref-dict",
                          str(tmp_path / "refs.json"), "--outdir", str(outdir), "--checkpoint",
@@ -162,10 +170,9 @@ def _two_style_tree(tmp_path):
 
 
 def _batch_styles_case(tmp_path, on_gpu):
-    import contextlib
     argv = _two_style_tree(tmp_path)
     outs = {}
-    with (contextlib.nullcontext() if on_gpu else _emulator.installed()):
+    with (contextlib.nullcontext() if on_gpu else _emulated()):
         for name, extra in (("loop", []), ("batch", ["--batch-styles"]), ("utts", ["--batch-utterances", "2"])):
             torch.manual_seed(7)
             ssc_decode.main(argv + ["--outdir", str(tmp_path / name)] + extra)
@@ -240,6 +247,7 @@ def test_cli_rejects_bad_argument_combinations(tmp_path):
 def _sharded_worker(rank, world, port, root, q):
     import torch.distributed as dist
     from pathlib import Path
+    from tests.test_parallel_gloo import cpu_barrier
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     torch.set_num_threads(2)  # two workers on the CI box's 8 cores
@@ -249,7 +257,7 @@ def _sharded_worker(rank, world, port, root, q):
     root = Path(root)
     argv = ["--dumpdir", str(root / "dump"), "--stats", str(root / "stats.joblib"), "--ref-dict", str(root / "refs.json"),
             "--checkpoint", str(root / "exp" / "checkpoint.pkl"), "--verbose", "0", "--outdir", str(root / "out")]
-    with _emulator.installed():
+    with _emulated():
         torch.manual_seed(7)
         ssc_decode.main(argv)
         err = None
@@ -258,7 +266,7 @@ def _sharded_worker(rank, world, port, root, q):
         except ValueError as e:
             err = str(e)
     q.put((rank, written, err))
-    dist.barrier()
+    cpu_barrier()
     dist.destroy_process_group()
 
 
