@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SRN_ABI_VERSION 3
+#define SRN_ABI_VERSION 4
 #define SRN_MAX_TAPS 16
 
 /* prologue activation applied to the gathered input elements */
@@ -46,6 +46,23 @@ enum {
   SRN_PREC_BF16X6 = 2  /* fp32-faithful emulation: exact (hi + mid + lo) split, 6 MFMA per product, fp32 accumulate:
                         * <= 2^-26 per product (below fp32's own rounding unit).  Kernels without a bf16x6 variant
                         * (generic conv_gemm, halo / strip, srn_hifigan_resunit) run their exact-fp32 path instead. */
+};
+/* SrnConvParams.route: which kernels srn_conv_gemm may choose from (testing / A-B timing; 0 in the product) */
+enum {
+  SRN_ROUTE_AUTO = 0,
+  SRN_ROUTE_TILED = 1,     /* tiled kernels only: no halo, no strip */
+  SRN_ROUTE_HALO = 2,      /* the halo kernel whenever it is eligible */
+  SRN_ROUTE_GENERIC = 3,   /* the generic conv_gemm kernel only */
+  SRN_ROUTE_STRIP = 4,     /* the strip kernel whenever it is eligible */
+  SRN_ROUTE_FAST_FP32 = 5  /* exact fp32 on conv_fast.hip's loop instead of conv_f32.hip's */
+};
+/* kernel families behind srn_conv_gemm (srn_conv_gemm_route) */
+enum {
+  SRN_FAMILY_GENERIC = 0, /* conv_gemm.hip */
+  SRN_FAMILY_F32 = 1,     /* conv_f32.hip */
+  SRN_FAMILY_FAST = 2,    /* conv_fast.hip */
+  SRN_FAMILY_HALO = 3,    /* conv_halo.hip */
+  SRN_FAMILY_STRIP = 4    /* conv_strip.hip (tile 0: the kernel follows from C_in and N) */
 };
 
 /*
@@ -103,9 +120,7 @@ typedef struct SrnConvParams {
   const float* res2; int64_t res2_bs; int32_t ld_res2;  /* second additive residual (HiFi-GAN stage sum) */
   float* out; int64_t out_bs, out_hs; int32_t ld_out;
   int32_t precision;  /* SRN_PREC_* */
-  int32_t no_halo;    /* kernel selection behind this entry point (testing / A-B timing): 0 = automatic, 1 = tiled kernels
-                       * only (no halo, no strip), 2 = halo kernel whenever eligible, 3 = generic conv_gemm kernel only,
-                       * 4 = strip kernel whenever eligible, 5 = exact fp32 on conv_fast.hip's loop instead of conv_f32.hip's */
+  int32_t route;      /* SRN_ROUTE_*: kernel selection behind this entry point (testing / A-B timing) */
   /* ws / ws_bytes: optional caller-owned workspace (16-byte aligned, at least srn_conv_gemm_workspace_bytes(p)
    * bytes, shared by all calls of one stream).  With it, launches whose tile grid cannot fill the chip are split
    * over K (conv_splitk.hip); without it (NULL) they run unsplit.  Results agree to fp32 summation order.
@@ -130,6 +145,9 @@ const char* srn_last_error(void);
 int srn_conv_gemm(const SrnConvParams* p, void* stream);
 /* bytes of workspace the split-K path would use for this call (0: the call is never split) */
 int64_t srn_conv_gemm_workspace_bytes(const SrnConvParams* p);
+/* the kernel srn_conv_gemm would launch for *p, without touching a device: out = {SRN_FAMILY_*, tile id, K slices}
+ * (K slices > 1: the f32 / fast slice launch followed by the split-K reduce).  Validates *p as srn_conv_gemm does. */
+int srn_conv_gemm_route(const SrnConvParams* p, int32_t out[3]);
 
 /*
  * GroupNorm(8 groups, eps) -> Mish -> (+ time_bias[c]) -> * mask   (Block1D tail + the time-embedding add of
@@ -239,7 +257,9 @@ typedef struct SrnResUnitParams {
   float post_div;           /* 0 or 1: none */
   float* out; int64_t out_bs;
   int32_t precision;        /* SRN_PREC_* */
+  int32_t route;            /* 0 = automatic; SRN_RESUNIT_ROUTE_SHARED: resunit.hip's exact-fp32 form (testing / A-B timing) */
 } SrnResUnitParams;
+enum { SRN_RESUNIT_ROUTE_SHARED = 1 };
 
 int srn_hifigan_resunit(const SrnResUnitParams* p, void* stream);
 
@@ -460,7 +480,9 @@ typedef struct SrnTnGemmParams {
                                  * as srn_conv_gemm's len_in does it in the forward */
   float* colsum;                /* or NULL; (M,), one problem, M % 4 == 0: alpha * sum_{item, t} a[item, t, m] -- a
                                  * conv's bias gradient (the column sums of dY), added in the same slice order */
+  int32_t route;                /* 0 = automatic; SRN_TN_ROUTE_GENERAL: the general kernel only (testing / A-B timing) */
 } SrnTnGemmParams;
+enum { SRN_TN_ROUTE_GENERAL = 1 };
 int srn_tn_gemm(const SrnTnGemmParams* p, void* stream);
 int64_t srn_tn_gemm_workspace_bytes(const SrnTnGemmParams* p);
 

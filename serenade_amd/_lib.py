@@ -15,6 +15,12 @@ ACT_NONE, ACT_LEAKY, ACT_SILU, ACT_MISH = 0, 1, 2, 3
 RES_NONE, RES_ADD, RES_AXPY = 0, 1, 2
 POST_NONE, POST_DIV, POST_TANH, POST_RELU, POST_LEAKY = 0, 1, 2, 3, 4
 PREC_FP32, PREC_BF16X3, PREC_BF16X6 = 0, 1, 2
+# SrnConvParams.route (testing / A-B timing): which kernels srn_conv_gemm may choose from
+ROUTE_AUTO, ROUTE_TILED, ROUTE_HALO, ROUTE_GENERIC, ROUTE_STRIP, ROUTE_FAST_FP32 = 0, 1, 2, 3, 4, 5
+# kernel families srn_conv_gemm_route reports
+FAMILY_GENERIC, FAMILY_F32, FAMILY_FAST, FAMILY_HALO, FAMILY_STRIP = 0, 1, 2, 3, 4
+RESUNIT_ROUTE_SHARED = 1  # SrnResUnitParams.route: resunit.hip's exact-fp32 form
+TN_ROUTE_GENERAL = 1  # SrnTnGemmParams.route: the general kernel only
 
 
 class SrnConvParams(ctypes.Structure):
@@ -32,7 +38,7 @@ class SrnConvParams(ctypes.Structure):
         ("res", c_void_p), ("res_bs", c_int64), ("res_hs", c_int64), ("ld_res", c_int32),
         ("res2", c_void_p), ("res2_bs", c_int64), ("ld_res2", c_int32),
         ("out", c_void_p), ("out_bs", c_int64), ("out_hs", c_int64), ("ld_out", c_int32),
-        ("precision", c_int32), ("no_halo", c_int32), ("ws", c_void_p), ("ws_bytes", c_int64),
+        ("precision", c_int32), ("route", c_int32), ("ws", c_void_p), ("ws_bytes", c_int64),
         ("w_hi", c_void_p), ("w_lo", c_void_p), ("gn_partials", c_void_p),
         ("out_tr", c_void_p), ("out_tr_bs", c_int64), ("ld_out_tr", c_int32), ("out_tr_col0", c_int32),
     ]
@@ -44,7 +50,7 @@ class SrnResUnitParams(ctypes.Structure):
         ("slope", c_float), ("x", c_void_p), ("x_bs", c_int64),
         ("w1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p),
         ("w1_hi", c_void_p), ("w2_hi", c_void_p), ("res2", c_void_p), ("res2_bs", c_int64),
-        ("post_div", c_float), ("out", c_void_p), ("out_bs", c_int64), ("precision", c_int32),
+        ("post_div", c_float), ("out", c_void_p), ("out_bs", c_int64), ("precision", c_int32), ("route", c_int32),
     ]
 
 
@@ -88,6 +94,7 @@ class SrnTnGemmParams(ctypes.Structure):
         ("out", c_void_p), ("out_bs", c_int64), ("out_hs", c_int64), ("ldc", c_int32),
         ("alpha", c_float), ("ws", c_void_p), ("ws_bytes", c_int64),
         ("n_inner", c_int32), ("a_is2", c_int64), ("b_is2", c_int64), ("len_b", c_void_p), ("colsum", c_void_p),
+        ("route", c_int32),
     ]
 
 
@@ -106,6 +113,7 @@ _SIGS = {
     "srn_last_error": (c_char_p, []),
     "srn_conv_gemm": (c_int, [POINTER(SrnConvParams), _P]),
     "srn_conv_gemm_workspace_bytes": (c_int64, [POINTER(SrnConvParams)]),
+    "srn_conv_gemm_route": (c_int, [POINTER(SrnConvParams), POINTER(c_int32)]),
     "srn_hifigan_resunit": (c_int, [POINTER(SrnResUnitParams), _P]),
     "srn_gn_mish_apply": (c_int, [_P, _P, _P, _P, _P, c_int64, _P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
     "srn_resblock_tail": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int,
@@ -187,7 +195,7 @@ def lib():
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args
-        if h.srn_abi_version() != 3:
+        if h.srn_abi_version() != 4:
             raise RuntimeError("libserenade_hip.so ABI version mismatch")
         _lib = h
     return _lib

@@ -251,17 +251,45 @@ __device__ __forceinline__ void splitk_store(const SrnConvParams& p, f32x16 (&ac
     }
 }
 
-// implemented in conv_halo.hip: receptive-field ("halo") variant for stride-1 multi-tap convs in split-bf16.
-// Returns 1 if it handled the launch, 0 if the shape is not eligible, < 0 on error.
-int srn_conv_halo_try(const SrnConvParams& p, int tile, hipStream_t stream);
-// implemented in conv_fast.hip: lean split-bf16 kernel for C_in % 32 == 0, k-major weights.  Same return codes.
-int srn_conv_fast_try(const SrnConvParams& p, int tile, hipStream_t stream, int ksplit = 1);
-// implemented in conv_f32.hip: the exact-fp32 contraction with a VALU-free main loop (tile ids 7, 9, 10).  Same return codes.
-int srn_conv_f32_try(const SrnConvParams& p, int tile, hipStream_t stream, int ksplit);
-// implemented in conv_splitk.hip: K slices for launches that cannot fill the chip (1 = do not split), the workspace
-// they need, and the reduction + epilogue over the partial sums.
-int srn_splitk_plan(const SrnConvParams& p);
+// Constants of the kernel choice (conv_gemm.hip's conv_route) shared with the kernels they describe.  The route is a
+// pure function of the params, so the chip's CU count is a constant here, not a device query.
+constexpr int SRN_NUM_CUS = 256;      // MI355X
+constexpr int SRN_HALO_MAX = 52;      // (k - 1) * dilation of the widest conv on the path (k 11, d 5 -> 50): the
+                                      // receptive-field rows the halo and strip kernels stage beyond their tile
+constexpr int SRN_STRIP_BM = 128;     // conv_strip.hip: output rows per tile (4 waves x 32 rows)
+constexpr int SRN_MAX_KSPLIT = 8;     // conv_splitk.hip: most K slices of one launch
+
+// lowest tap offset and the span (max - min) of the taps
+inline int srn_tap_span(const SrnConvParams& p, int& lo) {
+  lo = p.tap_off[0];
+  int hi = p.tap_off[0];
+  for (int i = 1; i < p.n_taps; ++i) {
+    lo = p.tap_off[i] < lo ? p.tap_off[i] : lo;
+    hi = p.tap_off[i] > hi ? p.tap_off[i] : hi;
+  }
+  return hi - lo;
+}
+
+// the B operand is a pre-split weight plane image (p.w_hi, and p.w_lo in bf16x6), shared by every (batch, head)
+inline bool srn_weight_planes(const SrnConvParams& p) {
+  return ((p.precision == SRN_PREC_BF16X3 && p.w_hi != nullptr) ||
+          (p.precision == SRN_PREC_BF16X6 && p.w_hi != nullptr && p.w_lo != nullptr)) &&
+         p.w_bs == 0 && p.w_hs == 0;
+}
+
+// LDS bytes of conv_strip.hip's kernel: all weights as (hi, lo) planes + the staged input image
+inline int srn_strip_lds_bytes(const SrnConvParams& p) {
+  return p.n_taps * p.C_in * p.N * 4 + (p.C_in / 32) * 2 * (SRN_STRIP_BM + SRN_HALO_MAX) * 64;
+}
+
+// The launchers of the kernel families behind srn_conv_gemm.  Each launches what it is told: `p` has been validated
+// and defaulted by srn_conv_gemm and routed by conv_route (conv_gemm.hip), which holds every eligibility rule.
+// `tile` is an id of conv_gemm.hip's tile table; `ksplit` > 1 (f32 / fast only) stores the partial sums of K slices
+// to p.ws for srn_splitk_reduce.  Return 0, or < 0 on error.
+int srn_conv_f32_launch(const SrnConvParams& p, int tile, int ksplit, hipStream_t stream);    // conv_f32.hip
+int srn_conv_fast_launch(const SrnConvParams& p, int tile, int ksplit, hipStream_t stream);   // conv_fast.hip
+int srn_conv_halo_launch(const SrnConvParams& p, int tile, int ksplit, hipStream_t stream);   // conv_halo.hip
+int srn_conv_strip_launch(const SrnConvParams& p, int tile, int ksplit, hipStream_t stream);  // conv_strip.hip
+// implemented in conv_splitk.hip: the workspace K slices need, and the reduction + epilogue over the partial sums
 int64_t srn_splitk_bytes(const SrnConvParams& p, int ksplit);
 int srn_splitk_reduce(const SrnConvParams& p, int ksplit, hipStream_t stream);
-// implemented in conv_strip.hip: thin convs (C_in, N in {32, 64}) with the whole weight tensor LDS-resident.
-int srn_conv_strip_try(const SrnConvParams& p, hipStream_t stream);

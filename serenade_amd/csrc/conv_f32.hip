@@ -485,7 +485,8 @@ int launch_f32_2(const SrnConvParams& p, hipStream_t stream, const int ksplit) {
   L.per_slice = (steps_all + ksplit - 1) / ksplit;
   const int64_t tiles_all = (int64_t)p.n_batch * p.n_head * L.m_tiles * L.n_tiles;
   const int64_t blocks = tiles_all * ksplit;
-  if (blocks <= 0 || blocks >= (1ll << 26)) return 0;  // the magic divisions hold below 2^26: other kernels take it
+  SRN_CHECK_ARG(blocks > 0 && blocks < (1ll << 26), "conv_f32: %lld workgroups (the magic divisions hold below 2^26)",
+                (long long)blocks);
   L.tiles_all = (int)tiles_all;
   L.d_per_z = make_fdiv((uint32_t)(L.m_tiles * L.n_tiles));
   L.d_band = make_fdiv((uint32_t)(TILE_BAND * L.n_tiles));
@@ -494,7 +495,7 @@ int launch_f32_2(const SrnConvParams& p, hipStream_t stream, const int ksplit) {
   L.d_cpt = make_fdiv((uint32_t)cpt);
   hipLaunchKernelGGL((conv_f32_kernel<C, ACT>), dim3((unsigned)blocks), dim3(256), C::SMEM_BYTES, stream, p, L);
   SRN_CHECK_LAUNCH();
-  return 1;
+  return 0;
 }
 
 template <class C>
@@ -505,32 +506,18 @@ int launch_f32(const SrnConvParams& p, hipStream_t stream, const int ksplit) {
 
 }  // namespace
 
-// Returns 1 if the launch was handled, 0 if the shape is not eligible (the caller goes on to conv_fast.hip), < 0 on
-// error.  `p` has been validated and defaulted by srn_conv_gemm.  Tile ids: 5 = 128 x 32, 6 = 128 x 128, 7 = 64 x 64, 9 = 64 x 128 (conv_fast.hip's
-// single-stage ids, same results bit for bit), 10 = 32 x 64 with the step split over two wave pairs, 11 = 64 x 64 with
-// two register sets (loads two steps ahead: small grids and split-K slices, where a workgroup is alone on its CU).
-int srn_conv_f32_try(const SrnConvParams& p, int tile, hipStream_t stream, int ksplit) {
-  if (p.precision != SRN_PREC_FP32 || p.w_nmajor) return 0;
-  if (p.C_in % BK != 0 || p.C_in0 % BK != 0) return 0;
-  if (p.C_w != p.C_in || p.ldw < p.n_taps * p.C_in) return 0;
-  if (!(p.pro_act == SRN_ACT_NONE || (p.pro_act == SRN_ACT_LEAKY && p.pro_slope >= 0.f && p.pro_slope <= 1.f))) return 0;
-  // 32-bit byte offsets inside one item of every operand
-  const int64_t lim = 0x7fffffffll;
-  if (((int64_t)p.T_in * p.ld_in0 + p.C_in) * 4 >= lim) return 0;
-  if (p.in1 && ((int64_t)p.T_in * p.ld_in1 + p.C_in) * 4 >= lim) return 0;
-  if (((int64_t)p.N * p.ldw + (int64_t)p.n_taps * p.C_in) * 4 >= lim) return 0;
-  if (p.T_in >= (1 << 24) || p.N >= (1 << 24) || p.ld_in0 >= (1 << 22) || p.ld_in1 >= (1 << 22) || p.ldw >= (1 << 22)) return 0;
-  const int64_t rows_all = (int64_t)(p.T_out - 1) * p.out_t_stride + p.out_t_off + 1;
-  if ((rows_all * p.ld_out + p.N) * 4 >= lim || (rows_all * p.ld_res + p.N) * 4 >= lim ||
-      (rows_all * p.ld_res2 + p.N) * 4 >= lim)
-    return 0;
+// Tile ids: 5 = 128 x 32, 7 = 64 x 64, 9 = 64 x 128 (conv_fast.hip's single-stage ids, same results bit for bit), 10 =
+// 32 x 64 with the step split over two wave pairs, 11 = 64 x 64 with two register sets (loads two steps ahead: small
+// grids and split-K slices, where a workgroup is alone on its CU).
+int srn_conv_f32_launch(const SrnConvParams& p, int tile, int ksplit, hipStream_t stream) {
   switch (tile) {
-    case 5: return p.geglu ? 0 : launch_f32<TCfg<128, 32, 32, 32, 1, 6>>(p, stream, ksplit);  // thin outputs (N = 32)
-    case 6: return launch_f32<TCfg<128, 128, 64, 64, 1, 3>>(p, stream, ksplit);
+    case 5: return launch_f32<TCfg<128, 32, 32, 32, 1, 6>>(p, stream, ksplit);  // thin outputs (N = 32)
     case 7: return launch_f32<TCfg<64, 64, 32, 32, 1, 6>>(p, stream, ksplit);
     case 9: return launch_f32<TCfg<64, 128, 32, 64, 1, 4>>(p, stream, ksplit);
-    case 10: return p.geglu ? 0 : launch_f32<TCfg<32, 64, 32, 32, 2, 6>>(p, stream, ksplit);
+    case 10: return launch_f32<TCfg<32, 64, 32, 32, 2, 6>>(p, stream, ksplit);
     case 11: return launch_f32<TCfg<64, 64, 32, 32, 1, 5, 2>>(p, stream, ksplit);
-    default: return 0;
+    default: break;
   }
+  srn_set_error("conv_f32: no tile id %d", tile);
+  return -1;
 }

@@ -584,7 +584,7 @@ int launch_fast3(const SrnConvParams& p, hipStream_t stream, const int ksplit) {
   hipLaunchKernelGGL((conv_fast_kernel<C, ACT, WPL>), dim3((unsigned)blocks), dim3(256), SMEM, stream, p, m_tiles,
                      n_tiles, ksplit);
   SRN_CHECK_LAUNCH();
-  return 1;
+  return 0;
 }
 
 template <class C, int ACT>
@@ -602,19 +602,12 @@ int launch_fast(const SrnConvParams& p, bool wpl, hipStream_t stream, int ks = 1
 
 }  // namespace
 
-// Returns 1 if the launch was handled, 0 if the shape is not eligible (caller falls back to the generic kernel),
-// < 0 on error.  `p` has been validated and defaulted by srn_conv_gemm.
-int srn_conv_fast_try(const SrnConvParams& p, int tile, hipStream_t stream, int ksplit) {
-  if (p.w_nmajor) return 0;
-  if (p.C_in % BK != 0 || p.C_in0 % BK != 0) return 0;
+int srn_conv_fast_launch(const SrnConvParams& p, int tile, int ksplit, hipStream_t stream) {
   const bool x6 = p.precision == SRN_PREC_BF16X6;
   const bool f32 = p.precision != SRN_PREC_BF16X3 && !x6;
-  const bool wpl = !f32 && p.w_hi != nullptr && (!x6 || p.w_lo != nullptr) && p.w_bs == 0 && p.w_hs == 0;
-  if (!wpl) {
-    // fp32 B rows walked contiguously over (tap, channel): needs the packed [tap][C_in] row layout, all of it live
-    if (p.C_w != p.C_in || p.ldw < p.n_taps * p.C_in) return 0;
-  }
+  const bool wpl = srn_weight_planes(p);
   if (ksplit > 1) {  // split-K launches always take the 64 x 64 tile (they exist because the grid is small)
+    SRN_CHECK_ARG(tile == 4, "conv_fast: K slices of tile %d", tile);
     if (f32) return launch_fast<FCfg<64, 64, 32, 32, 2, 0>>(p, false, stream, ksplit);
     if (x6) return launch_fast<FCfg<64, 64, 32, 32, 2, 2>>(p, wpl, stream, ksplit);
     return launch_fast<FCfg<64, 64, 32, 32>>(p, wpl, stream, ksplit);
@@ -626,14 +619,11 @@ int srn_conv_fast_try(const SrnConvParams& p, int tile, hipStream_t stream, int 
       case 3: return launch_fast<FCfg<64, 128, 32, 64, 2, 0>>(p, false, stream);
       case 4: return launch_fast<FCfg<64, 64, 32, 32, 2, 0>>(p, false, stream);
       case 5: return launch_fast<FCfg<128, 32, 32, 32, 2, 0>>(p, false, stream);
-      case 6: return launch_fast<FCfg<128, 128, 64, 64, 1, 0>>(p, false, stream);  // single LDS stage
-      case 7: return launch_fast<FCfg<64, 64, 32, 32, 1, 0>>(p, false, stream);
-      case 8: return launch_fast<FCfg<128, 64, 32, 64, 1, 0>>(p, false, stream);
+      case 7: return launch_fast<FCfg<64, 64, 32, 32, 1, 0>>(p, false, stream);  // single LDS stage
       case 9: return launch_fast<FCfg<64, 128, 32, 64, 1, 0>>(p, false, stream);
-      default: return 0;
+      default: break;
     }
-  }
-  if (x6) {
+  } else if (x6) {
     switch (tile) {
       // one LDS stage (48 KB, three workgroups per CU); the two-stage form (96 KB, one per CU) measured 0-40 % slower
       case 1: return launch_fast<FCfg<128, 128, 64, 64, 1, 2>>(p, wpl, stream);
@@ -642,22 +632,18 @@ int srn_conv_fast_try(const SrnConvParams& p, int tile, hipStream_t stream, int 
       case 4: return launch_fast<FCfg<64, 64, 32, 32, 2, 2>>(p, wpl, stream);
       case 5: return launch_fast<FCfg<128, 32, 32, 32, 2, 2>>(p, wpl, stream);
       case 7: return launch_fast<FCfg<64, 64, 32, 32, 1, 2>>(p, wpl, stream);
-      case 8: return launch_fast<FCfg<128, 64, 32, 64, 1, 2>>(p, wpl, stream);
-      case 9: return launch_fast<FCfg<64, 128, 32, 64, 1, 2>>(p, wpl, stream);
-      default: return 0;
+      default: break;
+    }
+  } else {
+    switch (tile) {
+      case 1: return launch_fast<FCfg<128, 128, 64, 64>>(p, wpl, stream);
+      case 2: return launch_fast<FCfg<128, 64, 32, 64>>(p, wpl, stream);
+      case 3: return launch_fast<FCfg<64, 128, 32, 64>>(p, wpl, stream);
+      case 4: return launch_fast<FCfg<64, 64, 32, 32>>(p, wpl, stream);
+      case 5: return launch_fast<FCfg<128, 32, 32, 32>>(p, wpl, stream);
+      default: break;
     }
   }
-  switch (tile) {
-    case 1: return launch_fast<FCfg<128, 128, 64, 64>>(p, wpl, stream);
-    case 2: return launch_fast<FCfg<128, 64, 32, 64>>(p, wpl, stream);
-    case 3: return launch_fast<FCfg<64, 128, 32, 64>>(p, wpl, stream);
-    case 4: return launch_fast<FCfg<64, 64, 32, 32>>(p, wpl, stream);
-    case 5: return launch_fast<FCfg<128, 32, 32, 32>>(p, wpl, stream);
-    case 6: return launch_fast<FCfg<128, 128, 64, 64, 1>>(p, wpl, stream);  // single LDS stage, 3 workgroups / CU
-    case 7: return launch_fast<FCfg<64, 64, 32, 32, 1>>(p, wpl, stream);
-    case 8: return launch_fast<FCfg<128, 64, 32, 64, 1>>(p, wpl, stream);
-    case 9: return launch_fast<FCfg<64, 128, 32, 64, 1>>(p, wpl, stream);
-    default: return 0;
-  }
+  srn_set_error("conv_fast: no tile id %d in precision %d", tile, p.precision);
+  return -1;
 }
-

@@ -405,17 +405,6 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const SrnConvParams p
   conv_epilogue<MT, NT>(p, acc, zb, zh, t0, n0, wm0, wn0, lane);
 }
 
-struct TileInfo {
-  int id, bm, bn, wn;
-  float base[3];  // measured relative efficiency of the tile shape on large grids: [fp32, split-bf16, bf16x6]
-};
-// id: 1 128x128 (64x64/wave) | 2 128x64 (32x64) | 3 64x128 (32x64) | 4 64x64 (32x32) | 5 128x32 (32x32)
-// (priors from tools/opbench.py --sweep on MI355X: in fp32 the MFMA phase is long and the small tile loses nothing;
-//  in split-bf16 the kernel is L2-traffic sensitive and bigger tiles win)
-const TileInfo kTiles[] = {{1, 128, 128, 64, {1.00f, 1.00f, 1.00f}}, {2, 128, 64, 64, {0.90f, 0.95f, 0.95f}},
-                           {3, 64, 128, 64, {0.92f, 0.97f, 0.97f}},  {4, 64, 64, 32, {0.97f, 0.85f, 0.90f}},
-                           {5, 128, 32, 32, {0.85f, 0.75f, 0.80f}}};
-
 template <class C, int ACT, int PREC>
 int launch_prec(const SrnConvParams& p, hipStream_t stream) {
   constexpr int SMEM = PREC == 1 ? 2 * (C::BM + C::BN) * 128 : C::SMEM_BYTES;
@@ -440,13 +429,103 @@ int launch_act(const SrnConvParams& p, hipStream_t stream) {
 template <class C>
 int launch(const SrnConvParams& p, hipStream_t stream) {
   if (p.pro_act == SRN_ACT_NONE) return launch_act<C, SRN_ACT_NONE>(p, stream);
-  if (p.pro_act == SRN_ACT_LEAKY) return launch_act<C, SRN_ACT_LEAKY>(p, stream);
-  // SiLU / Mish prologue: run-time activation, small tile only
-  return launch_act<Cfg<64, 64, 32, 32, C::NMAJ>, -1>(p, stream);
+  return launch_act<C, SRN_ACT_LEAKY>(p, stream);
+}
+
+// the generic kernel of this file: any shape the validation lets through
+int conv_generic_launch(const SrnConvParams& p, int tile, hipStream_t stream) {
+  if (!(p.pro_act == SRN_ACT_NONE || p.pro_act == SRN_ACT_LEAKY)) {
+    // SiLU / Mish prologue: run-time activation, small tile only
+    SRN_CHECK_ARG(tile == 4, "conv_gemm: run-time activation on tile %d", tile);
+    return p.w_nmajor ? launch_act<Cfg<64, 64, 32, 32, true>, -1>(p, stream)
+                      : launch_act<Cfg<64, 64, 32, 32, false>, -1>(p, stream);
+  }
+  if (p.w_nmajor) {
+    switch (tile) {
+      case 1: return launch<Cfg<128, 128, 64, 64, true>>(p, stream);
+      case 3: return launch<Cfg<64, 128, 32, 64, true>>(p, stream);
+      case 4: return launch<Cfg<64, 64, 32, 32, true>>(p, stream);
+      default: break;
+    }
+  } else {
+    switch (tile) {
+      case 1: return launch<Cfg<128, 128, 64, 64, false>>(p, stream);
+      case 2: return launch<Cfg<128, 64, 32, 64, false>>(p, stream);
+      case 3: return launch<Cfg<64, 128, 32, 64, false>>(p, stream);
+      case 4: return launch<Cfg<64, 64, 32, 32, false>>(p, stream);
+      case 5: return launch<Cfg<128, 32, 32, 32, false>>(p, stream);
+      default: break;
+    }
+  }
+  srn_set_error("conv_gemm: no tile id %d", tile);
+  return -1;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Kernel choice.  conv_route is a pure function of the (validated) params: no device is touched, so the CPU test suite
+// asks it (srn_conv_gemm_route) which kernel every op of a plan gets.
+
+// family bits of the tile table (conv_fast.hip's forms differ per precision; the generic kernel per B layout)
+enum : unsigned {
+  HAS_F32 = 1,                                      // conv_f32.hip
+  HAS_FAST_FP32 = 2, HAS_FAST_X3 = 4, HAS_FAST_X6 = 8,  // conv_fast.hip
+  HAS_FAST = HAS_FAST_FP32 | HAS_FAST_X3 | HAS_FAST_X6,
+  HAS_HALO = 16,                                    // conv_halo.hip (split-bf16 only)
+  HAS_GENERIC = 32, HAS_GENERIC_NMAJ = 64,          // this file, k-major / n-major weights
+};
+
+struct TileInfo {
+  int id, bm, bn, wm, wn, stages;  // output tile, per-wave tile, LDS stages of the conv_fast.hip / generic form
+  unsigned has;                    // families with a form of this id
+  int twin;                        // what a family without this id runs instead (0: it does not take the launch)
+  float base[3];                   // measured relative efficiency of the tile shape on large grids: [fp32, split-bf16,
+                                   // bf16x6]; pick_tile's model chooses among the ids that have one
+};
+// (priors from tools/opbench.py --sweep on MI355X: in fp32 the MFMA phase is long and the small tile loses nothing;
+//  in split-bf16 the kernel is L2-traffic sensitive and bigger tiles win)
+// Single-stage ids: an fp32 MFMA is 64 cycles (bf16x6: six MFMAs per product), so the loop is MFMA-bound with one LDS
+// stage and the halved footprint lets more workgroups share a CU.  conv_f32.hip's forms all stage once; conv_fast.hip's
+// bf16x6 id 1 is single-stage too.  Ids 10 and 11 exist only in conv_f32.hip: 10 splits each 32-deep step over two
+// wave pairs, 11 loads two steps ahead (small grids, split-K slices).  In exact fp32, id 4 (the small-grid 64 x 64) is
+// conv_f32.hip's 11 (B = 1 x T = 256: 16.8 -> 15.8 ms against conv_fast.hip's double-buffered tile).  Ids 6 and 8
+// (single-stage 128 x 128 / 128 x 64) are never chosen and have no kernel: forced, they run their twins.
+const TileInfo kTiles[] = {
+    {1, 128, 128, 64, 64, 2, HAS_FAST | HAS_HALO | HAS_GENERIC | HAS_GENERIC_NMAJ, 0, {1.00f, 1.00f, 1.00f}},
+    {2, 128, 64, 32, 64, 2, HAS_FAST | HAS_HALO | HAS_GENERIC, 0, {0.90f, 0.95f, 0.95f}},
+    {3, 64, 128, 32, 64, 2, HAS_FAST | HAS_HALO | HAS_GENERIC | HAS_GENERIC_NMAJ, 0, {0.92f, 0.97f, 0.97f}},
+    {4, 64, 64, 32, 32, 2, HAS_FAST | HAS_HALO | HAS_GENERIC | HAS_GENERIC_NMAJ, 11, {0.97f, 0.85f, 0.90f}},
+    {5, 128, 32, 32, 32, 2, HAS_F32 | HAS_FAST | HAS_HALO | HAS_GENERIC, 0, {0.85f, 0.75f, 0.80f}},
+    {6, 128, 128, 64, 64, 1, 0, 1, {}},
+    {7, 64, 64, 32, 32, 1, HAS_F32 | HAS_FAST_FP32 | HAS_FAST_X6, 4, {}},
+    {8, 128, 64, 32, 64, 1, 0, 2, {}},
+    {9, 64, 128, 32, 64, 1, HAS_F32 | HAS_FAST_FP32, 3, {}},
+    {10, 32, 64, 32, 32, 1, HAS_F32, 7, {}},
+    {11, 64, 64, 32, 32, 1, HAS_F32, 4, {}},
+};
+
+const TileInfo* tile_info(int id) {
+  for (const TileInfo& t : kTiles)
+    if (t.id == id) return &t;
+  return nullptr;
+}
+
+// the id a family runs for `id`: the id itself, else the first twin down the table's chain it has, else 0
+int tile_form(unsigned family, int id) {
+  for (int hop = 0; hop < 3; ++hop) {
+    const TileInfo* t = tile_info(id);
+    if (t == nullptr) return 0;
+    if (t->has & family) return id;
+    id = t->twin;
+  }
+  return 0;
+}
+
+unsigned fast_family(int precision) {
+  return precision == SRN_PREC_BF16X3 ? HAS_FAST_X3 : precision == SRN_PREC_BF16X6 ? HAS_FAST_X6 : HAS_FAST_FP32;
 }
 
 int pick_tile(const SrnConvParams& p) {
-  // Exact fp32: the single-LDS-stage forms (ids 6-9, conv_fast.hip) win on every shape of the path (opbench --fp32
+  // Exact fp32: the single-LDS-stage forms (ids 7, 9) win on every shape of the path (opbench --fp32
   // --sweep, r3): an fp32 MFMA is 64 cycles, so the loop is MFMA-bound with one stage, and the halved LDS footprint lets
   // 4-6 workgroups share a CU -- their staggered fills / epilogues cover each other, which two double-buffered
   // workgroups running in lockstep do not.  64 x 64 (id 7) for N = 512 .. 6144 (+4 .. +9 % over its two-stage form),
@@ -463,8 +542,9 @@ int pick_tile(const SrnConvParams& p) {
       // of 64 x 64 (5120 rows x 512 columns: the half-resolution levels) are 3 on some CUs and 2 on others; the same
       // output as 32 x 64 tiles (id 10, conv_f32.hip) is 5 on every CU
       const int64_t blocks10 = 2 * blocks7;
-      if (blocks10 <= 6 * 256 && p.T_out % 32 == 0 &&
-          1.05 * 0.5 * (double)((blocks10 + 255) / 256) < (double)((blocks7 + 255) / 256))
+      if (blocks10 <= 6 * SRN_NUM_CUS && p.T_out % 32 == 0 &&
+          1.05 * 0.5 * (double)((blocks10 + SRN_NUM_CUS - 1) / SRN_NUM_CUS) <
+              (double)((blocks7 + SRN_NUM_CUS - 1) / SRN_NUM_CUS))
         return 10;
       return 7;
     }
@@ -472,16 +552,18 @@ int pick_tile(const SrnConvParams& p) {
   float best = -1.f;
   int best_id = 4;
   const double z = (double)p.n_batch * p.n_head;
+  const double cus = SRN_NUM_CUS;
   for (const TileInfo& t : kTiles) {
+    if (t.base[0] == 0.f) continue;
     if (p.geglu && t.wn < 64) continue;
-    if (p.w_nmajor && !(t.id == 1 || t.id == 3 || t.id == 4)) continue;
+    if (p.w_nmajor && !(t.has & HAS_GENERIC_NMAJ)) continue;
     const double mt = (p.T_out + t.bm - 1) / t.bm, nt = (p.N + t.bn - 1) / t.bn;
     const double blocks = z * mt * nt;
     const double useful = ((double)p.T_out * p.N) / (mt * t.bm * nt * t.bn);
-    const double rounds = (blocks + 255.0) / 256.0;
-    double quant = blocks / (256.0 * (double)(int64_t)rounds);
+    const double rounds = (blocks + (cus - 1.0)) / cus;
+    double quant = blocks / (cus * (double)(int64_t)rounds);
     // fewer blocks than CUs idles CUs outright; beyond one round, co-resident blocks absorb part of the tail
-    if (blocks > 256.0) quant = 0.35 + 0.65 * quant;
+    if (blocks > cus) quant = 0.35 + 0.65 * quant;
     float score = (float)(useful * quant) * t.base[p.precision == SRN_PREC_BF16X3 ? 1 : (p.precision == SRN_PREC_BF16X6 ? 2 : 0)];
     // both operands split in the loop (Q K^T, P V): the 64x128 tile measured 5-10 % ahead of 128x128
     if (p.precision == SRN_PREC_BF16X3 && (p.w_hi == nullptr || p.w_bs != 0 || p.w_hs != 0) && t.id == 1)
@@ -500,12 +582,146 @@ int pick_tile(const SrnConvParams& p) {
   return best_id;
 }
 
-}  // namespace
+// conv_fast.hip: k-major weights, whole 32-channel chunks; fp32 B rows are walked contiguously over (tap, channel), so
+// without weight planes they need the packed [tap][C_in] row layout, all of it live
+bool fast_takes(const SrnConvParams& p) {
+  if (p.w_nmajor || p.C_in % 32 != 0 || p.C_in0 % 32 != 0) return false;
+  return srn_weight_planes(p) || (p.C_w == p.C_in && p.ldw >= p.n_taps * p.C_in);
+}
 
-extern "C" int srn_conv_gemm(const SrnConvParams* pp, void* stream_) {
+// conv_f32.hip: conv_fast.hip's fp32 shapes with a LeakyReLU slope in [0, 1] at most, 32-bit byte offsets inside one
+// item of every operand, and fewer workgroups than its magic divisions hold (2^26)
+bool f32_takes(const SrnConvParams& p, int tile, int ksplit) {
+  if (p.precision != SRN_PREC_FP32 || p.w_nmajor) return false;
+  if (p.C_in % 32 != 0 || p.C_in0 % 32 != 0) return false;
+  if (p.C_w != p.C_in || p.ldw < p.n_taps * p.C_in) return false;
+  if (!(p.pro_act == SRN_ACT_NONE || (p.pro_act == SRN_ACT_LEAKY && p.pro_slope >= 0.f && p.pro_slope <= 1.f))) return false;
+  const int64_t lim = 0x7fffffffll;
+  if (((int64_t)p.T_in * p.ld_in0 + p.C_in) * 4 >= lim) return false;
+  if (p.in1 && ((int64_t)p.T_in * p.ld_in1 + p.C_in) * 4 >= lim) return false;
+  if (((int64_t)p.N * p.ldw + (int64_t)p.n_taps * p.C_in) * 4 >= lim) return false;
+  if (p.T_in >= (1 << 24) || p.N >= (1 << 24) || p.ld_in0 >= (1 << 22) || p.ld_in1 >= (1 << 22) || p.ldw >= (1 << 22))
+    return false;
+  const int64_t rows_all = (int64_t)(p.T_out - 1) * p.out_t_stride + p.out_t_off + 1;
+  if ((rows_all * p.ld_out + p.N) * 4 >= lim || (rows_all * p.ld_res + p.N) * 4 >= lim ||
+      (rows_all * p.ld_res2 + p.N) * 4 >= lim)
+    return false;
+  const TileInfo& t = *tile_info(tile);
+  const int64_t blocks = (int64_t)p.n_batch * p.n_head * ((p.T_out + t.bm - 1) / t.bm) * ((p.N + t.bn - 1) / t.bn) * ksplit;
+  return blocks < (1ll << 26);
+}
+
+// conv_strip.hip: thin convs (<= 64 channels in and out) in split-bf16 with weight planes, LDS-resident weights
+bool strip_takes(const SrnConvParams& p) {
+  if (p.precision != SRN_PREC_BF16X3 || p.w_hi == nullptr || p.w_bs != 0 || p.w_hs != 0 || p.w_nmajor) return false;
+  if (p.n_head != 1 || p.in_stride != 1 || p.pad_reflect || p.geglu) return false;
+  if (!(p.C_in == 32 || p.C_in == 64) || p.C_in0 != p.C_in || !(p.N == 32 || p.N == 64)) return false;
+  if (!(p.pro_act == SRN_ACT_NONE || p.pro_act == SRN_ACT_LEAKY)) return false;
+  const bool force = p.route == SRN_ROUTE_STRIP;  // tests / A-B timing: take every structurally eligible shape
+  if (!force && p.T_out < 4 * SRN_STRIP_BM) return false;  // short sequences: the tiled kernels fill the chip better
+  int lo = 0;
+  if (srn_tap_span(p, lo) > SRN_HALO_MAX) return false;
+  const int smem = srn_strip_lds_bytes(p);
+  if (smem > 160 * 1024) return false;
+  // measured on the HiFi-GAN stages (8 x 245760 x 32 and 8 x 122880 x 64): ahead of the tiled kernels with >= 2
+  // workgroups per CU (32 channels: k3 0.242 -> 0.212, k7 0.328 -> 0.190, k11 0.355 -> 0.274 ms); with one (64
+  // channels: 95-160 KB) the exposed load latency loses (k3 0.201 -> 0.445 ms)
+  return force || smem <= 78 * 1024;
+}
+
+// conv_halo.hip: stride-1 multi-tap convs in split-bf16 stage the receptive-field tile once per channel chunk
+bool halo_takes(const SrnConvParams& p, int tile) {
+  if (p.precision != SRN_PREC_BF16X3 || p.n_taps < 2 || p.in_stride != 1 || p.pad_reflect || p.w_nmajor || p.geglu)
+    return false;
+  if (!(p.pro_act == SRN_ACT_NONE || p.pro_act == SRN_ACT_LEAKY)) return false;
+  const TileInfo* t = tile_info(tile);
+  if (t == nullptr || !(t->has & HAS_HALO)) return false;
+  int lo = 0;
+  if (srn_tap_span(p, lo) > SRN_HALO_MAX) return false;
+  // Measured on MI355X (tools/opbench.py --bf16x3 [--no-halo]): the halo image pays off when it is reused by many
+  // taps of a wide tile (N >= 128: k7 +15..17 %, k11 +22..25 %); for k3 and for the thin N = 32 / 64 tiles, whose
+  // steps are latency- not staging-bound, the generic kernel (3 resident blocks per CU) is as fast or faster.
+  return p.route == SRN_ROUTE_HALO || (p.N >= 128 && p.n_taps >= 7);
+}
+
+// K slices for this launch (1 = leave it alone).  Only shapes conv_fast.hip takes, with a plain or residual epilogue:
+// GEGLU and the transposed tail are never split (their GEMMs are wide).
+int splitk_plan(const SrnConvParams& p) {
+  if (p.geglu || p.out_tr != nullptr || p.N % 4 != 0 || !fast_takes(p)) return 1;
+  if (p.gn_partials && p.n_head != 1) return 1;
+  const int steps = p.n_taps * (p.C_in / 32);
+  // measured at B = 1 (1 workgroup per CU): ~4 us launch ramp + ~0.5 us per dependent k-step unsplit, vs ramp +
+  // steps / ks + a ~3 us reduce launch when split -- below ~24 steps the reduce eats the gain
+  if (steps < 24) return 1;
+  const int64_t tiles = (int64_t)p.n_batch * p.n_head * ((p.T_out + 63) / 64) * ((p.N + 63) / 64);
+  if (tiles > 192) return 1;
+  // one workgroup per CU: conv_f32.hip's two-steps-ahead tile covers its own latency, and a second workgroup on a CU
+  // halves both's matrix rate (B = 1 x T = 256 in place, same box: 15.44-15.52 ms at 256, 15.67 at round 3's 448 -- the
+  // double-buffered conv_fast.hip tile wanted ~1.75 per CU --, 15.49 at 288, 16.0-16.3 at 192 / 224 / 320)
+  int ks = (int)(SRN_NUM_CUS / tiles);
+  ks = ks > SRN_MAX_KSPLIT ? SRN_MAX_KSPLIT : ks;
+  ks = ks > steps / 4 ? steps / 4 : ks;  // at least four steps per slice
+  if (ks < 2) return 1;
+  const int per = (steps + ks - 1) / ks;
+  return (steps + per - 1) / per;  // no empty slice
+}
+
+struct ConvRoute {
+  int family, tile, ksplit;  // SRN_FAMILY_*, tile id (0 for the strip kernel), K slices
+};
+
+// Which kernel runs `p` (validated and defaulted).  Returns 0, or -1 for a tile id no kernel has.
+int conv_route(const SrnConvParams& p, ConvRoute& r) {
+  r = {SRN_FAMILY_GENERIC, 0, 1};
+  int tile = p.tile > 0 ? p.tile : pick_tile(p);
+  const TileInfo* t = tile_info(tile);
+  if (p.geglu && (t == nullptr || t->wn < 64)) tile = 1;  // the gate pairs columns n, n + 32 inside one wave
+  const bool fp32 = p.precision == SRN_PREC_FP32;
+  const bool use_f32 = fp32 && p.route != SRN_ROUTE_FAST_FP32;
+  if (p.ws != nullptr && p.tile <= 0 && p.route != SRN_ROUTE_GENERIC) {
+    // small grids with a deep contraction (B = 1 / short utterances): slice K over extra workgroups, reduce after
+    const int ks = splitk_plan(p);
+    if (ks > 1 && p.ws_bytes >= srn_splitk_bytes(p, ks)) {
+      if (use_f32 && f32_takes(p, 11, ks)) r = {SRN_FAMILY_F32, 11, ks};
+      else r = {SRN_FAMILY_FAST, 4, ks};  // splitk_plan splits only what conv_fast.hip takes
+      return 0;
+    }
+  }
+  if (p.route != SRN_ROUTE_TILED && p.route != SRN_ROUTE_GENERIC) {
+    if (strip_takes(p)) {
+      r.family = SRN_FAMILY_STRIP;
+      return 0;
+    }
+    if (halo_takes(p, tile)) {
+      r = {SRN_FAMILY_HALO, tile, 1};
+      return 0;
+    }
+  }
+  if (p.route != SRN_ROUTE_GENERIC) {
+    const int f32_tile = use_f32 ? tile_form(HAS_F32, tile) : 0;
+    if (f32_tile != 0 && f32_takes(p, f32_tile, 1)) {
+      r = {SRN_FAMILY_F32, f32_tile, 1};
+      return 0;
+    }
+    const int fast_tile = tile_form(fast_family(p.precision), tile);
+    if (fast_tile != 0 && fast_takes(p)) {
+      r = {SRN_FAMILY_FAST, fast_tile, 1};
+      return 0;
+    }
+  }
+  int gen_tile = tile_form(p.w_nmajor ? HAS_GENERIC_NMAJ : HAS_GENERIC, tile);
+  if (gen_tile == 0 && p.w_nmajor) gen_tile = 4;  // the n-major forms fall back to 64 x 64
+  SRN_CHECK_ARG(gen_tile != 0, "conv_gemm: unknown tile id %d", tile);
+  // SiLU / Mish prologue: run-time activation, small tile only
+  if (!(p.pro_act == SRN_ACT_NONE || p.pro_act == SRN_ACT_LEAKY)) gen_tile = 4;
+  r.tile = gen_tile;
+  return 0;
+}
+
+// validate and default the params of one call
+int conv_params(const SrnConvParams* pp, SrnConvParams& p) {
   SRN_CHECK_ARG(pp != nullptr, "conv_gemm: null params");
-  SrnConvParams p = *pp;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  p = *pp;
   SRN_CHECK_ARG(p.in0 && p.w && p.out, "conv_gemm: null in0/w/out");
   SRN_CHECK_ARG(p.n_batch > 0 && p.n_head > 0 && p.T_in > 0 && p.T_out > 0 && p.N > 0, "conv_gemm: bad sizes");
   SRN_CHECK_ARG(p.C_in > 0 && p.C_in % 4 == 0, "conv_gemm: C_in (%d) must be a positive multiple of 4", p.C_in);
@@ -545,69 +761,47 @@ extern "C" int srn_conv_gemm(const SrnConvParams* pp, void* stream_) {
     for (int i = 0; i < p.n_taps; ++i)
       SRN_CHECK_ARG(p.tap_off[i] > -p.T_in && p.tap_off[i] < p.T_in, "conv_gemm: reflect pad wider than the input");
   }
+  return 0;
+}
 
-  int tile = p.tile > 0 ? p.tile : pick_tile(p);
-  if (p.geglu && !(tile == 1 || tile == 2 || tile == 3 || tile == 6 || tile == 8 || tile == 9)) tile = 1;
-  if (p.ws != nullptr && p.tile <= 0 && p.no_halo != 3) {
-    // small grids with a deep contraction (B = 1 / short utterances): slice K over extra workgroups, reduce after
-    const int ks = srn_splitk_plan(p);
-    if (ks > 1 && p.ws_bytes >= srn_splitk_bytes(p, ks)) {
-      // exact fp32: conv_f32.hip's 64 x 64 tile with loads two steps ahead (id 11; B = 1 x T = 256: 16.8 -> 15.8 ms
-      // against conv_fast.hip's double-buffered tile here and for the unsplit small grids below)
-      int r = 0;
-      if (p.precision == SRN_PREC_FP32 && p.no_halo != 5) r = srn_conv_f32_try(p, 11, stream, ks);
-      if (r == 0) r = srn_conv_fast_try(p, 4, stream, ks);
-      if (r < 0) return r;
-      if (r == 1) return srn_splitk_reduce(p, ks, stream);
-    }
+}  // namespace
+
+extern "C" int srn_conv_gemm(const SrnConvParams* pp, void* stream_) {
+  SrnConvParams p;
+  if (const int e = conv_params(pp, p)) return e;
+  ConvRoute r;
+  if (const int e = conv_route(p, r)) return e;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  int e = 0;
+  switch (r.family) {
+    case SRN_FAMILY_F32: e = srn_conv_f32_launch(p, r.tile, r.ksplit, stream); break;
+    case SRN_FAMILY_FAST: e = srn_conv_fast_launch(p, r.tile, r.ksplit, stream); break;
+    case SRN_FAMILY_HALO: e = srn_conv_halo_launch(p, r.tile, r.ksplit, stream); break;
+    case SRN_FAMILY_STRIP: e = srn_conv_strip_launch(p, r.tile, r.ksplit, stream); break;
+    default: e = conv_generic_launch(p, r.tile, stream); break;
   }
-  if (p.no_halo != 1 && p.no_halo != 3) {
-    // thin convs (<= 64 channels in and out): persistent strip kernel with LDS-resident weights
-    const int r = srn_conv_strip_try(p, stream);
-    if (r != 0) return r < 0 ? r : 0;
-  }
-  if (p.no_halo != 1 && p.no_halo != 3) {
-    // stride-1 multi-tap convs in split-bf16: stage the receptive-field tile once per channel chunk
-    const int r = srn_conv_halo_try(p, tile, stream);
-    if (r != 0) return r < 0 ? r : 0;
-  }
-  if (p.no_halo != 3) {  // 3: generic kernel only (testing / A-B timing)
-    if (p.precision == SRN_PREC_FP32 && p.no_halo != 5) {  // 5: conv_fast.hip's fp32 form (A-B timing against conv_f32.hip)
-      const int r = srn_conv_f32_try(p, tile == 4 ? 11 : tile, stream, 1);  // 4: small grids -> its two-steps-ahead form
-      if (r != 0) return r < 0 ? r : 0;
-    }
-    if (tile == 10) tile = 7;  // the split-step tile exists only in conv_f32.hip
-    if (tile == 11) tile = 4;  // ... and so does the two-steps-ahead tile: conv_fast.hip's double-buffered twin
-    const int r = srn_conv_fast_try(p, tile, stream);
-    if (r != 0) return r < 0 ? r : 0;
-  }
-  // single-stage ids exist only in conv_fast.hip: their two-stage twins here
-  tile = tile == 6 ? 1 : (tile == 7 || tile == 10 || tile == 11) ? 4 : tile == 8 ? 2 : tile == 9 ? 3 : tile;
-  if (p.w_nmajor) {
-    switch (tile) {
-      case 1: return launch<Cfg<128, 128, 64, 64, true>>(p, stream);
-      case 3: return launch<Cfg<64, 128, 32, 64, true>>(p, stream);
-      default: return launch<Cfg<64, 64, 32, 32, true>>(p, stream);
-    }
-  }
-  switch (tile) {
-    case 1: return launch<Cfg<128, 128, 64, 64, false>>(p, stream);
-    case 2: return launch<Cfg<128, 64, 32, 64, false>>(p, stream);
-    case 3: return launch<Cfg<64, 128, 32, 64, false>>(p, stream);
-    case 4: return launch<Cfg<64, 64, 32, 32, false>>(p, stream);
-    case 5: return launch<Cfg<128, 32, 32, 32, false>>(p, stream);
-    default: break;
-  }
-  srn_set_error("conv_gemm: unknown tile id %d", tile);
-  return -1;
+  if (e == 0 && r.ksplit > 1) e = srn_splitk_reduce(p, r.ksplit, stream);
+  return e;
+}
+
+extern "C" int srn_conv_gemm_route(const SrnConvParams* pp, int32_t out[3]) {
+  SRN_CHECK_ARG(out != nullptr, "conv_gemm_route: null out");
+  SrnConvParams p;
+  if (const int e = conv_params(pp, p)) return e;
+  ConvRoute r;
+  if (const int e = conv_route(p, r)) return e;
+  out[0] = r.family;
+  out[1] = r.tile;
+  out[2] = r.ksplit;
+  return 0;
 }
 
 extern "C" int64_t srn_conv_gemm_workspace_bytes(const SrnConvParams* pp) {
-  if (pp == nullptr) return 0;
-  SrnConvParams p = *pp;
-  if (p.C_in0 <= 0 || p.C_in0 > p.C_in) p.C_in0 = p.C_in;
-  if (p.C_w <= 0 || p.C_w > p.C_in) p.C_w = p.C_in;
-  if (p.n_head <= 0 || p.n_batch <= 0 || p.T_out <= 0 || p.N <= 0 || p.C_in <= 0 || p.n_taps <= 0) return 0;
-  const int ks = srn_splitk_plan(p);
-  return ks > 1 ? srn_splitk_bytes(p, ks) : 0;
+  SrnConvParams p;
+  if (pp == nullptr || conv_params(pp, p) != 0) return 0;
+  p.ws = &p;  // the route of this call with a workspace of any size attached
+  p.ws_bytes = INT64_MAX;
+  ConvRoute r;
+  if (conv_route(p, r) != 0 || r.ksplit <= 1) return 0;
+  return srn_splitk_bytes(p, r.ksplit);
 }

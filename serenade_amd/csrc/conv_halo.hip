@@ -14,7 +14,7 @@
 namespace {
 
 constexpr int BK = 32;
-constexpr int HALO_MAX = 52;  // (k-1)*dilation of the widest conv on the path: k 11, d 5 -> 50
+constexpr int HALO_MAX = SRN_HALO_MAX;
 
 template <int BM_, int BN_, int WM_, int WN_>
 struct HCfg {
@@ -255,7 +255,7 @@ int launch_halo(const SrnConvParams& p, int min_off, int halo, hipStream_t strea
   hipLaunchKernelGGL((conv_halo_kernel<C, ACT>), dim3((unsigned)blocks), dim3(256), C::SMEM_BYTES, stream, p, m_tiles,
                      n_tiles, min_off, halo);
   SRN_CHECK_LAUNCH();
-  return 1;
+  return 0;
 }
 
 template <class C>
@@ -266,26 +266,18 @@ int launch_halo_act(const SrnConvParams& p, int min_off, int halo, hipStream_t s
 
 }  // namespace
 
-int srn_conv_halo_try(const SrnConvParams& p, int tile, hipStream_t stream) {
-  if (p.precision != SRN_PREC_BF16X3 || p.n_taps < 2 || p.in_stride != 1 || p.pad_reflect || p.w_nmajor || p.geglu)
-    return 0;
-  if (!(p.pro_act == SRN_ACT_NONE || p.pro_act == SRN_ACT_LEAKY)) return 0;
-  int lo = p.tap_off[0], hi = p.tap_off[0];
-  for (int i = 1; i < p.n_taps; ++i) {
-    lo = p.tap_off[i] < lo ? p.tap_off[i] : lo;
-    hi = p.tap_off[i] > hi ? p.tap_off[i] : hi;
-  }
-  if (hi - lo > HALO_MAX) return 0;
-  // Measured on MI355X (tools/opbench.py --bf16x3 [--no-halo]): the halo image pays off when it is reused by many
-  // taps of a wide tile (N >= 128: k7 +15..17 %, k11 +22..25 %); for k3 and for the thin N = 32 / 64 tiles, whose
-  // steps are latency- not staging-bound, the generic kernel (3 resident blocks per CU) is as fast or faster.
-  if (p.no_halo != 2 && !(p.N >= 128 && p.n_taps >= 7)) return 0;
+int srn_conv_halo_launch(const SrnConvParams& p, int tile, int ksplit, hipStream_t stream) {
+  int lo = 0;
+  const int halo = srn_tap_span(p, lo);
+  SRN_CHECK_ARG(ksplit == 1 && halo <= HALO_MAX, "conv_halo: tap span %d, %d K slices", halo, ksplit);
   switch (tile) {
-    case 1: return launch_halo_act<HCfg<128, 128, 64, 64>>(p, lo, hi - lo, stream);
-    case 2: return launch_halo_act<HCfg<128, 64, 32, 64>>(p, lo, hi - lo, stream);
-    case 3: return launch_halo_act<HCfg<64, 128, 32, 64>>(p, lo, hi - lo, stream);
-    case 4: return launch_halo_act<HCfg<64, 64, 32, 32>>(p, lo, hi - lo, stream);
-    case 5: return launch_halo_act<HCfg<128, 32, 32, 32>>(p, lo, hi - lo, stream);
-    default: return 0;
+    case 1: return launch_halo_act<HCfg<128, 128, 64, 64>>(p, lo, halo, stream);
+    case 2: return launch_halo_act<HCfg<128, 64, 32, 64>>(p, lo, halo, stream);
+    case 3: return launch_halo_act<HCfg<64, 128, 32, 64>>(p, lo, halo, stream);
+    case 4: return launch_halo_act<HCfg<64, 64, 32, 32>>(p, lo, halo, stream);
+    case 5: return launch_halo_act<HCfg<128, 32, 32, 32>>(p, lo, halo, stream);
+    default: break;
   }
+  srn_set_error("conv_halo: no tile id %d", tile);
+  return -1;
 }

@@ -3,7 +3,7 @@
 // At B = 1 / short utterances the N = 512 convs and projections of the UNet (K = 512 ... 3072) are 32-64 tiles of
 // 64 x 64: a quarter of the CUs walk 16-96 dependent k-steps each (measured 31 us average over 413 launches per
 // B = 1 x T = 256 Euler step, 55 % of the GPU time).  Here the (tap, channel) steps are sliced over `ksplit` extra
-// workgroup sets (conv_fast.hip, ksplit > 1) that store raw fp32 partial sums to a workspace slab
+// workgroup sets (conv_f32.hip / conv_fast.hip, ksplit > 1; conv_gemm.hip's conv_route decides) that store raw fp32 partial sums to a workspace slab
 // [slice][z][T_out][N]; this file's kernel sums the slices IN SLICE ORDER (bit-reproducible, no atomics) and applies
 // the one epilogue every contraction has (alpha, bias, output mask, residual add / axpy, second residual, post op,
 // strided rows, GroupNorm partial sums).  GEGLU and the transposed tail are never split (their GEMMs are wide).
@@ -14,8 +14,6 @@
 #include "serenade_hip.h"
 
 namespace {
-
-constexpr int MAX_KSPLIT = 8;
 
 // one workgroup per (z, 32-row, 32-column) block: thread -> (row tid / 8, 4 columns at 4 (tid % 8)); the block is
 // exactly one GroupNorm partial-sum tile
@@ -32,19 +30,19 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const SrnConvParams 
   const int zh = z - zb * p.n_head;
   const int row = mt * 32 + (tid >> 3);
   const int col = nt * 32 + (tid & 7) * 4;
-  const bool ok = row < p.T_out && col < p.N;  // N % 4 == 0 (srn_splitk_plan)
+  const bool ok = row < p.T_out && col < p.N;  // N % 4 == 0 (conv_route)
   const int64_t Z = (int64_t)p.n_batch * p.n_head;
   const int64_t slab = Z * p.T_out * p.N;
   float v[4] = {0.f, 0.f, 0.f, 0.f};
   if (ok) {
-    // all (up to MAX_KSPLIT) slices' loads are issued back to back from clamped addresses and summed in slice order:
+    // all (up to SRN_MAX_KSPLIT) slices' loads are issued back to back from clamped addresses and summed in slice order:
     // a run-time-length load loop pays one dependent memory round trip per slice (measured 5.9 us per call at B = 1)
     const float* w = reinterpret_cast<const float*>(p.ws) + ((int64_t)z * p.T_out + row) * p.N + col;
-    float4 q[MAX_KSPLIT];
+    float4 q[SRN_MAX_KSPLIT];
 #pragma unroll
-    for (int s = 0; s < MAX_KSPLIT; ++s) q[s] = *reinterpret_cast<const float4*>(w + min(s, ksplit - 1) * slab);
+    for (int s = 0; s < SRN_MAX_KSPLIT; ++s) q[s] = *reinterpret_cast<const float4*>(w + min(s, ksplit - 1) * slab);
 #pragma unroll
-    for (int s = 0; s < MAX_KSPLIT; ++s) {
+    for (int s = 0; s < SRN_MAX_KSPLIT; ++s) {
       const float on = s < ksplit ? 1.f : 0.f;
       v[0] += on * q[s].x, v[1] += on * q[s].y, v[2] += on * q[s].z, v[3] += on * q[s].w;
     }
@@ -97,32 +95,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const SrnConvParams 
 }
 
 }  // namespace
-
-// K slices for this launch (1 = leave it alone).  Only shapes conv_fast.hip takes, with a plain or residual epilogue.
-int srn_splitk_plan(const SrnConvParams& p) {
-  if (p.geglu || p.out_tr != nullptr || p.w_nmajor || p.N % 4 != 0) return 1;
-  if (p.C_in % 32 != 0 || p.C_in0 % 32 != 0) return 1;
-  const bool wpl = ((p.precision == SRN_PREC_BF16X3 && p.w_hi != nullptr) ||
-                    (p.precision == SRN_PREC_BF16X6 && p.w_hi != nullptr && p.w_lo != nullptr)) &&
-                   p.w_bs == 0 && p.w_hs == 0;
-  if (!wpl && (p.C_w != p.C_in || p.ldw < p.n_taps * p.C_in)) return 1;
-  if (p.gn_partials && p.n_head != 1) return 1;
-  const int steps = p.n_taps * (p.C_in / 32);
-  // measured at B = 1 (1 workgroup per CU): ~4 us launch ramp + ~0.5 us per dependent k-step unsplit, vs ramp +
-  // steps / ks + a ~3 us reduce launch when split -- below ~24 steps the reduce eats the gain
-  if (steps < 24) return 1;
-  const int64_t tiles = (int64_t)p.n_batch * p.n_head * ((p.T_out + 63) / 64) * ((p.N + 63) / 64);
-  if (tiles > 192) return 1;
-  // one workgroup per CU: conv_f32.hip's two-steps-ahead tile covers its own latency, and a second workgroup on a CU
-  // halves both's matrix rate (B = 1 x T = 256 in place, same box: 15.44-15.52 ms at 256, 15.67 at round 3's 448 -- the
-  // double-buffered conv_fast.hip tile wanted ~1.75 per CU --, 15.49 at 288, 16.0-16.3 at 192 / 224 / 320)
-  int ks = (int)(256 / tiles);
-  ks = ks > MAX_KSPLIT ? MAX_KSPLIT : ks;
-  ks = ks > steps / 4 ? steps / 4 : ks;  // at least four steps per slice
-  if (ks < 2) return 1;
-  const int per = (steps + ks - 1) / ks;
-  return (steps + per - 1) / per;  // no empty slice
-}
 
 int64_t srn_splitk_bytes(const SrnConvParams& p, int ksplit) {
   return (int64_t)ksplit * p.n_batch * p.n_head * p.T_out * p.N * (int64_t)sizeof(float);

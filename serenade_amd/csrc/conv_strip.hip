@@ -15,8 +15,8 @@
 
 namespace {
 
-constexpr int BM = 128;        // output rows per tile: 4 waves x 32 rows
-constexpr int HALO_MAX = 52;   // (k - 1) * dilation of the widest conv on the path (k 11, d 5 -> 50)
+constexpr int BM = SRN_STRIP_BM;  // output rows per tile: 4 waves x 32 rows
+constexpr int HALO_MAX = SRN_HALO_MAX;
 constexpr int HR_MAX = BM + HALO_MAX;
 
 __device__ __attribute__((aligned(256))) float g_zero_strip[64];
@@ -183,7 +183,7 @@ int launch_strip(const SrnConvParams& p, int min_off, int halo, hipStream_t stre
   hipLaunchKernelGGL((conv_strip_kernel<CIN, NT, ACT>), dim3(grid), dim3(256), smem, stream, p, min_off, halo,
                      tiles_per_z, (int)n_tiles);
   SRN_CHECK_LAUNCH();
-  return 1;
+  return 0;
 }
 
 template <int CIN, int NT>
@@ -194,28 +194,13 @@ int launch_strip_act(const SrnConvParams& p, int min_off, int halo, hipStream_t 
 
 }  // namespace
 
-// Returns 1 if the launch was handled, 0 if the shape is not eligible, < 0 on error.
-int srn_conv_strip_try(const SrnConvParams& p, hipStream_t stream) {
-  if (p.precision != SRN_PREC_BF16X3 || p.w_hi == nullptr || p.w_bs != 0 || p.w_hs != 0 || p.w_nmajor) return 0;
-  if (p.n_head != 1 || p.in_stride != 1 || p.pad_reflect || p.geglu) return 0;
-  if (!(p.C_in == 32 || p.C_in == 64) || p.C_in0 != p.C_in || !(p.N == 32 || p.N == 64)) return 0;
-  if (!(p.pro_act == SRN_ACT_NONE || p.pro_act == SRN_ACT_LEAKY)) return 0;
-  const bool force = p.no_halo == 4;  // tests / A-B timing: take every structurally eligible shape
-  if (!force && p.T_out < 4 * BM) return 0;  // short sequences: the tiled kernels fill the chip better
-  int lo = p.tap_off[0], hi = p.tap_off[0];
-  for (int i = 1; i < p.n_taps; ++i) {
-    lo = p.tap_off[i] < lo ? p.tap_off[i] : lo;
-    hi = p.tap_off[i] > hi ? p.tap_off[i] : hi;
-  }
-  if (hi - lo > HALO_MAX) return 0;
-  const int smem = p.n_taps * p.C_in * p.N * 4 + (p.C_in / 32) * 2 * HR_MAX * 64;
-  if (smem > 160 * 1024) return 0;
-  // measured on the HiFi-GAN stages (8 x 245760 x 32 and 8 x 122880 x 64): ahead of the tiled kernels with >= 2
-  // workgroups per CU (32 channels: k3 0.242 -> 0.212, k7 0.328 -> 0.190, k11 0.355 -> 0.274 ms); with one (64
-  // channels: 95-160 KB) the exposed load latency loses (k3 0.201 -> 0.445 ms)
-  if (!force && smem > 78 * 1024) return 0;
-  if (p.C_in == 32 && p.N == 32) return launch_strip_act<32, 1>(p, lo, hi - lo, stream);
-  if (p.C_in == 32 && p.N == 64) return launch_strip_act<32, 2>(p, lo, hi - lo, stream);
-  if (p.C_in == 64 && p.N == 32) return launch_strip_act<64, 1>(p, lo, hi - lo, stream);
-  return launch_strip_act<64, 2>(p, lo, hi - lo, stream);
+int srn_conv_strip_launch(const SrnConvParams& p, int, int ksplit, hipStream_t stream) {
+  int lo = 0;
+  const int halo = srn_tap_span(p, lo);
+  SRN_CHECK_ARG(ksplit == 1 && halo <= HALO_MAX && (p.C_in == 32 || p.C_in == 64) && (p.N == 32 || p.N == 64),
+                "conv_strip: C_in %d, N %d, tap span %d, %d K slices", p.C_in, p.N, halo, ksplit);
+  if (p.C_in == 32 && p.N == 32) return launch_strip_act<32, 1>(p, lo, halo, stream);
+  if (p.C_in == 32 && p.N == 64) return launch_strip_act<32, 2>(p, lo, halo, stream);
+  if (p.C_in == 64 && p.N == 32) return launch_strip_act<64, 1>(p, lo, halo, stream);
+  return launch_strip_act<64, 2>(p, lo, halo, stream);
 }

@@ -416,13 +416,10 @@ extern "C" int srn_hifigan_resunit(const SrnResUnitParams* pp, void* stream_) {
     return p.C == 32 ? launch_resunit<RCfg<32, 1>>(p, stream) : launch_resunit<RCfg<64, 1>>(p, stream);
   }
   // exact fp32: resunit_f32.hip's form of this kernel (same results bit for bit, ~no vector-ALU work beside the fp32
-  // MFMAs); SERENADE_AMD_RESUNIT_SHARED_FP32=1 keeps this file's instantiation (A-B timing, bit-identity test)
-  {
-    const char* e = getenv("SERENADE_AMD_RESUNIT_SHARED_FP32");
-    if (!(e && e[0] == '1')) {
-      const int r = srn_resunit_f32_try(p, stream);
-      if (r != 0) return r < 0 ? r : 0;
-    }
+  // MFMAs); route SRN_RESUNIT_ROUTE_SHARED keeps this file's instantiation (A-B timing, bit-identity test)
+  if (p.route != SRN_RESUNIT_ROUTE_SHARED) {
+    const int r = srn_resunit_f32_try(p, stream);
+    if (r != 0) return r < 0 ? r : 0;
   }
   // eight waves per workgroup (A/B on the B = 8 x T = 1024 vocoder, 4 -> 8 waves: k 3 units 0.62 -> 0.51 ms,
   // k 7 1.17 -> 1.05, k 11 1.74 -> 1.61 at C = 64; all 18 units 16.7 -> 14.9 ms)

@@ -386,7 +386,7 @@ int plan_split(const SrnTnGemmParams& p, int TB, int& k_per) {
   int ks = 1;
   // ~3 workgroups per CU wanted, never fewer than 8 slabs per slice.  Swept on the training step's shapes
   // (tools/tnbench.py, B = 4 x L = 1024): targets 256 / 384 / 512 / 768 / 1024 give 57 / 67 / 75 / 79 / 77 TFLOP/s overall
-  static const int target = getenv("SRN_TN_TARGET") ? atoi(getenv("SRN_TN_TARGET")) : 768;
+  constexpr int target = 768;
   if (tiles < target / 2) {
     ks = (int)((target + tiles - 1) / tiles);
     const int64_t cap = K / (8 * BK);
@@ -399,7 +399,7 @@ int plan_split(const SrnTnGemmParams& p, int TB, int& k_per) {
   return ks < 1 ? 1 : ks;
 }
 
-// tile edge.  Measured on the training step's shapes (tools/tnbench.py, B = 4 x L = 1024; SRN_TN_TILE forces one):
+// tile edge.  Measured on the training step's shapes (tools/tnbench.py, B = 4 x L = 1024):
 // 64 wins only where 128-tiles leave the chip nearly empty even after slicing -- the two narrow weight gradients
 // (512 x 256: 27 vs 32 us, 80 x 512: 22 vs 31 us) and short contractions that cannot be sliced further
 // (attention dV at L = 512: 62 vs 71 us); everywhere else 128 is 8-40 % faster (twice the MFMA work per LDS byte)
@@ -409,8 +409,6 @@ int64_t ws_floats(const SrnTnGemmParams& p, int ks) {
 }
 
 int tile_edge(const SrnTnGemmParams& p) {
-  static const int forced = getenv("SRN_TN_TILE") ? atoi(getenv("SRN_TN_TILE")) : 0;
-  if (forced == 64 || forced == 128) return forced;
   const int64_t tiles128 = (int64_t)((p.M + 127) / 128) * ((p.N + 127) / 128) * p.n_shifts * p.n_batch * p.n_head;
   const int64_t K = (int64_t)p.n_items * p.T_a;
   if (tiles128 <= 8) return 64;
@@ -467,11 +465,9 @@ extern "C" int srn_tn_gemm(const SrnTnGemmParams* pp, void* stream_) {
   const int64_t gz = (int64_t)p.n_batch * p.n_head * ks;
   SRN_CHECK_ARG(gz <= 65535 && (int64_t)m_tiles * n_tiles < (1ll << 31), "tn_gemm: grid too large");
   const dim3 grid(m_tiles * n_tiles, p.n_shifts, (unsigned)gz);
-  // the scalar-walk form: every slab inside one item, 32-bit byte offsets inside an item (SRN_TN_GENERAL=1: A-B timing
-  // and the bit-identity test keep the general kernel)
-  const char* const env_general = getenv("SRN_TN_GENERAL");
-  const bool general_only = env_general != nullptr && env_general[0] == '1';
-  const bool lean = !general_only && p.n_inner <= 1 && p.T_a % BK == 0 && k_per % BK == 0 &&
+  // the scalar-walk form: every slab inside one item, 32-bit byte offsets inside an item (route SRN_TN_ROUTE_GENERAL:
+  // A-B timing and the bit-identity test keep the general kernel)
+  const bool lean = p.route != SRN_TN_ROUTE_GENERAL && p.n_inner <= 1 && p.T_a % BK == 0 && k_per % BK == 0 &&
                     (int64_t)p.T_a * p.lda * 4 < 0x7fffffffll &&
                     ((int64_t)p.T_b + (int64_t)p.T_a * p.stride + 64) * p.ldb * 4 < 0x7fffffffll;
   auto kern = lean ? (TB == 64 ? tn_lean_kernel<64> : tn_lean_kernel<128>)

@@ -21,7 +21,6 @@ ATTENTION_PRECISION = None  # Q K^T / P V of the estimator's self-attention; Non
 
 def attention_precision():
     return DEFAULT_PRECISION if ATTENTION_PRECISION is None else ATTENTION_PRECISION
-NO_HALO = False  # True: force the generic kernel everywhere (A/B timing)
 # Split-K for launches whose tile grid cannot fill the chip (B = 1 / short utterances; conv_splitk.hip): every ConvOp
 # is handed the per-device workspace below and the library decides per call.  SERENADE_AMD_SPLITK=0 turns it off.
 SPLITK = os.environ.get("SERENADE_AMD_SPLITK", "1") != "0"
@@ -63,8 +62,8 @@ class ConvOp:
                  bias=None, len_in=None, len_out=None, in_stride=1, reflect=False, pro_act=ACT_NONE, pro_slope=0.0,
                  alpha=1.0, beta=0.0, geglu=False, res=None, res_mode=RES_NONE, res_bs=0, res_hs=0, ld_res=0, res2=None,
                  res2_bs=0, ld_res2=0, post=POST_NONE, post_div=1.0, out_bs=0, out_hs=0, out_t_stride=1, out_t_off=0,
-                 gn_partials=None, N_out=0, tile=0, precision=None, no_halo=False, out_tr=None, out_tr_bs=0,
-                 ld_out_tr=0, out_tr_col0=0):
+                 gn_partials=None, N_out=0, tile=0, precision=None, route=_lib.ROUTE_AUTO, out_tr=None, out_tr_bs=0,
+                 ld_out_tr=0, out_tr_col0=0, no_halo=None):
         p = SrnConvParams()
         p.n_batch, p.n_head, p.T_in, p.T_out = int(n_batch), int(n_head), int(T_in), int(T_out)
         p.C_in, p.C_in0, p.C_w, p.N, p.N_out = int(C_in), int(C_in0), int(C_w), int(N), int(N_out)
@@ -87,7 +86,8 @@ class ConvOp:
         p.gn_partials = _ptr(gn_partials)
         p.out_tr, p.out_tr_bs, p.ld_out_tr, p.out_tr_col0 = _ptr(out_tr), int(out_tr_bs), int(ld_out_tr), int(out_tr_col0)
         p.precision = int(DEFAULT_PRECISION if precision is None else precision)
-        p.no_halo = 1 if NO_HALO else int(no_halo)  # 0 auto, 1 tiled kernels only, 2 force halo, 3 generic kernel only, 4 force strip
+        # _lib.ROUTE_*: kernel selection (testing / A-B timing); no_halo is its former name, same values
+        p.route = int(route if no_halo is None else no_halo)
         self.p = p
         self._fn = _lib.lib().srn_conv_gemm
         self._wplanes = None
@@ -139,7 +139,7 @@ class ResUnitOp:
         self._build(**kw)
 
     def _build(self, *, x, w1, b1, w2, b2, out, n_batch, T, C, k, dilation, slope, res2=None, post_div=0.0,
-               precision=None):
+               precision=None, route=0):
         p = SrnResUnitParams()
         p.n_batch, p.T, p.C, p.k, p.dilation, p.slope = int(n_batch), int(T), int(C), int(k), int(dilation), float(slope)
         p.x, p.x_bs = _ptr(x), int(T) * int(C)
@@ -148,6 +148,7 @@ class ResUnitOp:
         p.post_div = float(post_div)
         p.out, p.out_bs = _ptr(out), int(T) * int(C)
         p.precision = int(DEFAULT_PRECISION if precision is None else precision)
+        p.route = int(route)  # _lib.RESUNIT_ROUTE_SHARED: resunit.hip's exact-fp32 form (testing / A-B timing)
         self._wplanes = None
         if p.precision == _lib.PREC_BF16X3 and w1.is_cuda:
             self._wplanes = (weight_planes(w1, C, k, C, k * C), weight_planes(w2, C, k, C, k * C))
@@ -248,11 +249,11 @@ class TnGemmOp:
 
     def __init__(self, *, a, b, out, n_items, T_a, T_b, M, N, lda, ldb, ldc, shifts=(0,), stride=1, n_batch=1,
                  n_head=1, a_bs=0, a_hs=0, a_is=0, b_bs=0, b_hs=0, b_is=0, out_bs=0, out_hs=0, alpha=1.0, n_inner=1,
-                 a_is2=0, b_is2=0, len_b=None, colsum=None):
+                 a_is2=0, b_is2=0, len_b=None, colsum=None, route=0):
         self.kw = dict(a=a, b=b, out=out, n_items=n_items, T_a=T_a, T_b=T_b, M=M, N=N, lda=lda, ldb=ldb, ldc=ldc,
                        shifts=tuple(int(v) for v in shifts), stride=stride, n_batch=n_batch, n_head=n_head, a_bs=a_bs,
                        a_hs=a_hs, a_is=a_is, b_bs=b_bs, b_hs=b_hs, b_is=b_is, out_bs=out_bs, out_hs=out_hs, alpha=alpha,
-                       n_inner=n_inner, a_is2=a_is2, b_is2=b_is2, len_b=len_b, colsum=colsum)
+                       n_inner=n_inner, a_is2=a_is2, b_is2=b_is2, len_b=len_b, colsum=colsum, route=route)
         p = _lib.SrnTnGemmParams()
         p.n_batch, p.n_head, p.n_items, p.T_a, p.T_b = n_batch, n_head, n_items, T_a, T_b
         p.stride, p.n_shifts, p.M, p.N = stride, len(shifts), M, N
@@ -265,6 +266,7 @@ class TnGemmOp:
         if len_b is not None and len_b.dtype != torch.int32:
             raise TypeError("TnGemmOp: len_b must be int32")
         p.len_b, p.colsum = _ptr(len_b), _ptr(colsum)
+        p.route = int(route)  # _lib.TN_ROUTE_GENERAL: the general kernel only (testing / A-B timing)
         self._fn = _lib.lib().srn_tn_gemm
         need = int(_lib.lib().srn_tn_gemm_workspace_bytes(ctypes.byref(p)))
         self._ws = None

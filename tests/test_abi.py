@@ -35,7 +35,7 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
 
 
 def test_error_reporting_without_gpu(lib):
-    assert lib.srn_abi_version() == 3
+    assert lib.srn_abi_version() == 4
     assert lib.srn_conv_gemm(None, None) == -1
     assert b"null params" in lib.srn_last_error()
     p = _lib.SrnConvParams()

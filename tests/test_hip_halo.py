@@ -48,11 +48,11 @@ def test_halo_matches_generic_and_spec(case):
     if "leaky" in ex:
         base.update(pro_act=_lib.ACT_LEAKY, pro_slope=ex["leaky"])
     outs = {}
-    for name, no_halo in (("halo", 2), ("generic", 1)):
+    for name, route in (("halo", _lib.ROUTE_HALO), ("generic", _lib.ROUTE_TILED)):
         out = torch.zeros(B, Tn, N, device=dev)
         gn = torch.zeros(B, (Tn + 31) // 32, N // 32, 2, device=dev) if ex.get("gn") else None
         ops.ConvOp(in0=x.to(dev), w=w.to(dev), bias=bias.to(dev), res=res.to(dev), out=out, gn_partials=gn,
-                   len_in=None if lens is None else lens.to(dev), no_halo=no_halo, **base)()
+                   len_in=None if lens is None else lens.to(dev), route=route, **base)()
         outs[name] = (out.cpu(), None if gn is None else gn.cpu())
     assert nerr(outs["halo"][0], outs["generic"][0]) < 2e-6  # same split, same products, same k order per tap
     cpu_out = torch.zeros(B, Tn, N)
@@ -72,24 +72,24 @@ def test_halo_concat_input_and_transposed_phase():
     kw = dict(in1_bs=Tn * C1, ld_in1=C1, C_in0=C0, n_batch=B, T_in=Tn, T_out=Tn, C_in=C0 + C1, N=N, in0_bs=Tn * C0,
               ld_in0=C0, ldw=3 * (C0 + C1), out_bs=Tn * N, ld_out=N, taps=ops.conv_taps(3))
     got = {}
-    for no_halo in (2, 1):
+    for route in (_lib.ROUTE_HALO, _lib.ROUTE_TILED):
         out = torch.zeros(B, Tn, N, device=dev)
-        ops.ConvOp(in0=x.to(dev), in1=s.to(dev), w=w.to(dev), out=out, no_halo=no_halo, **kw)()
-        got[no_halo] = out.cpu()
+        ops.ConvOp(in0=x.to(dev), in1=s.to(dev), w=w.to(dev), out=out, route=route, **kw)()
+        got[route] = out.cpu()
     ref = torch.zeros(B, Tn, N)
     _emulator.emul_conv(dict(kw, in0=x, in1=s, w=w, out=ref))
-    assert nerr(got[2], got[1]) < 2e-6 and nerr(got[2], ref) < 1e-4
+    assert nerr(got[_lib.ROUTE_HALO], got[_lib.ROUTE_TILED]) < 2e-6 and nerr(got[_lib.ROUTE_HALO], ref) < 1e-4
     # a 2-tap transposed-conv phase with strided output rows
     wt = rnd(C0, 32, 10, seed=8) / 10.0
     To = 5 * Tn
     outs = {}
-    for no_halo in (2, 1):
+    for route in (_lib.ROUTE_HALO, _lib.ROUTE_TILED):
         out = torch.zeros(B, To, 32, device=dev)
         for r, (taps, wp) in enumerate(ops.convtranspose_phases(wt, 5, 3)):
             ops.ConvOp(in0=x.to(dev), w=wp.to(dev), out=out, n_batch=B, T_in=Tn, T_out=Tn, C_in=C0, N=32,
                        in0_bs=Tn * C0, ld_in0=C0, ldw=wp.shape[1], out_bs=To * 32, ld_out=32, taps=taps,
-                       out_t_stride=5, out_t_off=r, pro_act=_lib.ACT_LEAKY, pro_slope=0.1, no_halo=no_halo)()
-        outs[no_halo] = out.cpu()
+                       out_t_stride=5, out_t_off=r, pro_act=_lib.ACT_LEAKY, pro_slope=0.1, route=route)()
+        outs[route] = out.cpu()
     ref = torch.nn.functional.conv_transpose1d(torch.nn.functional.leaky_relu(x, 0.1).transpose(1, 2), wt, None,
                                                stride=5, padding=3, output_padding=1).transpose(1, 2)
-    assert nerr(outs[2], outs[1]) < 2e-6 and nerr(outs[2], ref) < 1e-4
+    assert nerr(outs[_lib.ROUTE_HALO], outs[_lib.ROUTE_TILED]) < 2e-6 and nerr(outs[_lib.ROUTE_HALO], ref) < 1e-4

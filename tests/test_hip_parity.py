@@ -85,8 +85,8 @@ def run_conv_both(dev, kw, tol=None, tiles=(0,)):
     base = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in kw.items()}
     tol = KTOL.k if tol is None else tol
     # two kernel families behind the one entry point: the specialised ones (conv_fast / halo / strip; auto) and the
-    # generic conv_gemm kernel (no_halo=3 forces it)
-    # (exact fp32 has two implementations of the specialised loop: conv_f32.hip, and conv_fast.hip's behind no_halo=5)
+    # generic conv_gemm kernel (ROUTE_GENERIC forces it)
+    # (exact fp32 has two implementations of the specialised loop: conv_f32.hip, and conv_fast.hip's behind ROUTE_FAST_FP32)
     variants = ("auto", "generic", "fast_fp32")
     for tile, variant in [(t, u) for t in tiles for u in variants]:
         cpu = {}
@@ -107,13 +107,13 @@ def run_conv_both(dev, kw, tol=None, tiles=(0,)):
         gpu = {k: m(v) for k, v in cpu.items()}
         gpu["tile"] = tile
         if variant == "generic":
-            if gpu.get("no_halo"):
+            if gpu.get("route"):
                 continue
-            gpu["no_halo"] = 3
+            gpu["route"] = _lib.ROUTE_GENERIC
         if variant == "fast_fp32":
-            if gpu.get("no_halo") or serenade_amd.get_precision() != "fp32":
+            if gpu.get("route") or serenade_amd.get_precision() != "fp32":
                 continue
-            gpu["no_halo"] = 5
+            gpu["route"] = _lib.ROUTE_FAST_FP32
         op = ops.ConvOp(**gpu)
         op()
         torch.cuda.synchronize()
@@ -129,12 +129,12 @@ def rnd(*s, seed=0):
     return torch.from_numpy(np.random.default_rng(seed).standard_normal(s).astype(np.float32))
 
 
-ALL_TILES = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11)  # 11: 64 x 64, loads two steps ahead; 6-9: the single-LDS-stage forms; 10: 32 x 64, step split over wave pairs
+ALL_TILES = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11)  # 11: 64 x 64, loads two steps ahead; 7, 9: the single-LDS-stage forms (6, 8 run their twins 1, 2); 10: 32 x 64, step split over wave pairs
 
 
 def test_library_exports_and_error_path(dev):
     lib = _lib.lib()
-    assert lib.srn_abi_version() == 3
+    assert lib.srn_abi_version() == 4
     rc = lib.srn_conv_gemm(None, None)
     assert rc != 0 and b"null" in lib.srn_last_error()
 

@@ -85,9 +85,9 @@ def test_resunit_vs_conv1d(dev, C, k, d):
 
 
 @pytest.mark.parametrize("C", [32, 64])
-def test_resunit_fp32_forms_agree_bit_for_bit(dev, C, monkeypatch):
+def test_resunit_fp32_forms_agree_bit_for_bit(dev, C):
     """exact fp32 has two implementations of the fused unit: resunit_f32.hip (buffer addressing, no vector-ALU work beside
-    the fp32 MFMAs) and resunit.hip's instantiation (SERENADE_AMD_RESUNIT_SHARED_FP32=1): same LDS image, same MFMA order,
+    the fp32 MFMAs) and resunit.hip's instantiation (RESUNIT_ROUTE_SHARED): same LDS image, same MFMA order,
     same epilogue order -- every unit of the path, sequence ends inside / across tiles, must agree bit for bit"""
     if serenade_amd.get_precision() != "fp32":
         pytest.skip("fp32 arm only")
@@ -100,11 +100,10 @@ def test_resunit_fp32_forms_agree_bit_for_bit(dev, C, monkeypatch):
             b1, b2 = rnd(C, seed=case + 4, scale=0.1).to(dev), rnd(C, seed=case + 5, scale=0.1).to(dev)
             res2 = rnd(B, T, C, seed=case + 6).to(dev) if with_sum else None
             outs = []
-            for shared in ("0", "1"):
-                monkeypatch.setenv("SERENADE_AMD_RESUNIT_SHARED_FP32", shared)
+            for route in (0, _lib.RESUNIT_ROUTE_SHARED):
                 out = torch.full((B, T, C), float("nan"), device=dev)
                 ops.ResUnitOp(x=x, w1=w1, b1=b1, w2=w2, b2=b2, out=out, n_batch=B, T=T, C=C, k=k, dilation=d, slope=slope,
-                              res2=res2, post_div=3.0 if with_sum else 0.0)()
+                              res2=res2, post_div=3.0 if with_sum else 0.0, route=route)()
                 torch.cuda.synchronize()
                 outs.append(out)
             assert torch.isfinite(outs[0]).all()

@@ -2,7 +2,9 @@
 """Per-op timing of the headline workload's plan (developer tool, GPU only): times every distinct conv_gemm call of
 one Euler step + the vocoder and prints achieved TFLOP/s per shape, sorted by time share.
 
-    python tools/opbench.py [tile-override]
+    python tools/opbench.py [--fp32 | --bf16x6] [--no-halo] [--sweep]
+
+--no-halo times every op on the tiled kernels only (no halo, no strip kernel).
 """
 import collections
 import os
@@ -12,7 +14,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
-from serenade_amd import ops  # noqa: E402
+from serenade_amd import _lib, ops  # noqa: E402
+
+ROUTE = _lib.ROUTE_AUTO  # the route every timed ConvOp is rebuilt with (main: --no-halo)
 
 
 def sig(k):
@@ -28,6 +32,8 @@ def time_ops(oplist, reps=20):
     for op in oplist:
         if not isinstance(op, (ops.ConvOp, ops.ResUnitOp)):
             continue
+        if isinstance(op, ops.ConvOp) and ROUTE != _lib.ROUTE_AUTO:
+            op = ops.ConvOp(**dict(op.kw, route=ROUTE))
         op()
         torch.cuda.synchronize()
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -60,19 +66,19 @@ def sweep(oplist, reps=5):
     for op in oplist:
         if isinstance(op, ops.ConvOp) and sig(op.kw) not in seen:
             seen[sig(op.kw)] = op
-    print(f"{'Z':>4} {'T_out':>7} {'N':>5} {'K':>6} taps nmaj geglu |  auto    t1     t4     t6     t7     t8     t9    t10    t11   old7   old9  (TF/s)")
+    print(f"{'Z':>4} {'T_out':>7} {'N':>5} {'K':>6} taps nmaj geglu |  auto    t1     t4     t7     t9    t10    t11   old7   old9  (TF/s)")
     for k, op in seen.items():
         Z, T, N, K, taps, nmaj, geglu, st, gn, act = k
         fl = 2.0 * Z * T * N * K
         res = []
-        for tile in (0, 1, 4, 6, 7, 8, 9, 10, 11, -7, -9):
+        for tile in (0, 1, 4, 7, 9, 10, 11, -7, -9):
             if tile in (2, 5) and nmaj:
                 res.append(float("nan"))
                 continue
             if geglu and abs(tile) in (4, 5, 7, 10, 11):
                 res.append(float("nan"))
                 continue
-            o2 = ops.ConvOp(**dict(op.kw, tile=abs(tile), no_halo=5 if tile < 0 else op.kw.get("no_halo", False)))
+            o2 = ops.ConvOp(**dict(op.kw, tile=abs(tile), route=_lib.ROUTE_FAST_FP32 if tile < 0 else ROUTE))
             try:
                 o2()
             except RuntimeError:  # a tile id the kernel that takes this shape does not have
@@ -91,8 +97,9 @@ def sweep(oplist, reps=5):
 
 
 def main():
+    global ROUTE
     if "--no-halo" in sys.argv:
-        ops.NO_HALO = True
+        ROUTE = _lib.ROUTE_TILED
     import serenade_amd
     serenade_amd.set_precision("fp32" if "--fp32" in sys.argv else ("bf16x6" if "--bf16x6" in sys.argv else "bf16x3"))
     dev = torch.device("cuda:0")
