@@ -2,7 +2,8 @@
 """Headline benchmark: converted source mel frames / second of the Serenade audio-infilling inference path
 (GST style encoder -> content encoder -> 1-D UNet flow-matching Euler ODE -> HiFi-GAN vocoder) on MI355X.
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1               # the headline alone
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full        # the headline, then every secondary measurement
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,10 +13,14 @@ in HBM; with N > 1 every rank converts its own batch (utterances shard embarrass
 converted waveforms are gathered on rank 0 over RCCL inside the timed region.  Rank 0 prints ONE JSON line.
 
 The top-level `value` / `ms_per_step` / `dtype` / `roofline` are measured in the REFERENCE's precision: exact fp32
-contraction on v_mfma_f32_32x32x2_f32.  The faster split-bf16 product mode (operands as bf16 hi+lo, 3 MFMA per
-product: inside the north-star tolerances but narrower than fp32) and the fp32-faithful bf16x6 emulation (exact
-three-way operand split, 6 MFMA per product) are timed in the same run and reported under `split_bf16_mode` /
-`fp32_emulated_bf16x6_mode`; the north-star's other sizes under `sweep`; the CPU oracle under `cpu_baseline`.
+contraction on v_mfma_f32_32x32x2_f32.  A plain run does only that: it sets up, warms up, times the steps, writes
+`--dump-outputs` if asked and prints the line.  `--full` goes on, after the headline, to what else is measured: the
+faster split-bf16 product mode (operands as bf16 hi+lo, 3 MFMA per product: inside the north-star tolerances but
+narrower than fp32) and the fp32-faithful bf16x6 emulation (exact three-way operand split, 6 MFMA per product) under
+`split_bf16_mode` / `fp32_emulated_bf16x6_mode`; exact fp32 with bf16x3 attention under
+`fp32_with_bf16x3_attention_mode`; the training step under `train_step`; the analysis stage under `analysis_stage`;
+the north-star's other sizes under `sweep`; the CPU oracle under `cpu_baseline`.  The `--no-*` options leave single
+legs out of a `--full` run; `--modes` picks the timed contraction modes of either kind of run.
 
 `--dump-outputs DIR` writes what the headline mode's last timed step handed back (the mel batch and, on rank 0, the
 waveforms) as DIR/mel.npy and DIR/wave.npy in float32, so that two builds can be compared output for output: inputs and
@@ -309,18 +314,20 @@ def dump_outputs(d, arrays):
     return {"dir": d, "arrays": info}
 
 
-def main():
-    global B_PER_GPU, T_SRC, T_REF, N_EULER
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="after the headline, measure everything else: the other "
+                    "contraction modes, fp32 with bf16x3 attention, the training step, the analysis stage, the size "
+                    "sweep and the CPU baselines (one GPU; the --no-* options leave single legs out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sweep", action="store_true", help="skip the north-star size sweep (profiling runs)")
     ap.add_argument("--no-mixed", action="store_true", help="skip the fp32 + bf16x3-attention secondary key (profiling runs)")
     ap.add_argument("--no-train", action="store_true", help="skip the estimator training-step line (SURVEY 8 f4)")
-    ap.add_argument("--modes", default="fp32,bf16x6,bf16x3", help="contraction modes to time; the first is the "
-                                                                  "headline (profiling runs pass one)")
+    ap.add_argument("--modes", default=None, help="contraction modes to time; the first is the headline (default: "
+                                                  "fp32, with --full fp32,bf16x6,bf16x3)")
     ap.add_argument("--force-dist", action="store_true", help="initialise the RCCL process group and run the "
                     "waveform gather even with one rank (single-GPU rehearsal of the N>1 path)")
     ap.add_argument("--no-post", action="store_true", help="skip the analysis-stage (f1) secondary key")
@@ -332,11 +339,30 @@ def main():
     ap.add_argument("--euler", type=int, default=N_EULER, help="Euler ODE steps")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the headline mode's last timed "
                     "step returned (mel, waveform) to DIR/<name>.npy in float32, under 64 MB in all")
-    args = ap.parse_args()
-    B_PER_GPU, T_SRC, T_REF, N_EULER = args.batch, args.frames, args.ref_frames, args.euler
-    modes = [m for m in args.modes.split(",") if m]
-    assert modes and all(m in DTYPE for m in modes), f"--modes takes {sorted(DTYPE)}"
+    args = ap.parse_args(argv)
+    if args.modes is None:
+        args.modes = "fp32,bf16x6,bf16x3" if args.full else "fp32"
+    args.modes = [m for m in args.modes.split(",") if m]
+    assert args.modes and all(m in DTYPE for m in args.modes), f"--modes takes {sorted(DTYPE)}"
     assert args.steps >= 1 and args.warmup >= 0, "--steps >= 1, --warmup >= 0"
+    return args
+
+
+def secondary_legs(args, rank, world):
+    """the measurements after the headline's modes: none in a plain run; with --full, on one GPU, every leg its
+    --no-* option leaves in (the bf16x3-attention leg needs fp32 among the modes)"""
+    if not args.full or rank != 0 or world != 1:
+        return set()
+    legs = {"mixed": "fp32" in args.modes and not args.no_mixed, "train": not args.no_train,
+            "post": not args.no_post, "sweep": not args.no_sweep, "cpu_baseline": not args.no_cpu_baseline}
+    return {k for k, on in legs.items() if on}
+
+
+def main():
+    global B_PER_GPU, T_SRC, T_REF, N_EULER
+    args = parse_args()
+    B_PER_GPU, T_SRC, T_REF, N_EULER = args.batch, args.frames, args.ref_frames, args.euler
+    modes = args.modes
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -552,9 +578,10 @@ def main():
             out.setdefault("multi_gpu", {})[k] = head[k]
     for m in modes[1:]:
         out[MODE_KEY[m]] = results[m]
-    if "fp32" in modes and world == 1 and not args.no_mixed:
+    legs = secondary_legs(args, rank, world)
+    if "mixed" in legs:
         out["fp32_with_bf16x3_attention_mode"] = mixed_attention()
-    if rank == 0 and world == 1 and not args.no_train:
+    if "train" in legs:
         # a secondary line: it must never cost the headline its JSON
         try:
             serenade_amd.set_precision(modes[0])
@@ -567,7 +594,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             out["train_step"] = {"error": f"{type(e).__name__}: {e}"[:500]}
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_post:
+    if "post" in legs:
         # SURVEY 8 f1, a secondary key: the analysis front-end between HiFi-GAN and SiFiGAN (CheapTrick, mel-cepstrum, D4C,
         # F0 contours, excitation; fp64, one workgroup per 5 ms frame) on the waveforms of the same batch size, and the
         # SiFiGAN generator behind it -- tools/worldbench.py's numbers
@@ -582,9 +609,9 @@ def main():
         except Exception as e:  # noqa: BLE001  (never costs the headline its JSON)
             out["analysis_stage"] = {"error": f"{type(e).__name__}: {e}"[:300]}
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_sweep:
+    if "sweep" in legs:
         out["sweep"] = sweep()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if "cpu_baseline" in legs:
         out["cpu_baseline"] = cpu_baseline(sd, gsd)
         if "train_step" in out and "error" not in out["train_step"]:
             try:

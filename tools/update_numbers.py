@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Developer tool: rewrite the numbers block (between the `<!-- numbers:begin -->` / `<!-- numbers:end -->` markers) of
-DESIGN.md and README.md from ONE bench.py JSON line, so every figure in the two documents comes from the same run.
+DESIGN.md and README.md from ONE `bench.py --full` JSON line, so every figure in the two documents comes from the same run.
 
     python3 tools/update_numbers.py <file holding the bench line> ["label of the run"]
 """
@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     d = json.loads([ln for ln in open(sys.argv[1]) if ln.startswith("{")][-1])
-    label = sys.argv[2] if len(sys.argv) > 2 else "bench.py defaults"
+    label = sys.argv[2] if len(sys.argv) > 2 else "bench.py --full"
     f = lambda v, n=0: f"{v:,.{n}f}".replace(",", " ")
     r = d["roofline"]
     x6, x3, mix = d["fp32_emulated_bf16x6_mode"], d["split_bf16_mode"], d["fp32_with_bf16x3_attention_mode"]
