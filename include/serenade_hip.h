@@ -37,7 +37,8 @@ enum {
   SRN_POST_DIV = 1, /* v / post_div (HiFi-GAN: cs / num_blocks, hifigan.py:186) */
   SRN_POST_TANH = 2,
   SRN_POST_RELU = 3,
-  SRN_POST_LEAKY = 4 /* LeakyReLU with slope post_div */
+  SRN_POST_LEAKY = 4, /* LeakyReLU with slope post_div */
+  SRN_POST_GELU = 5   /* GELU (erf form, nn.GELU()): HuBERT / ContentVec feature convs and feed-forward */
 };
 /* arithmetic of the contraction */
 enum {
@@ -519,6 +520,33 @@ int srn_token_attn_fwd(const float* q, const float* k, const float* v, float* p,
 /* dq (B, F); dk_part, dv_part (B, n_tok, F): per-item terms, summed over items by the caller (srn_colsum). */
 int srn_token_attn_bwd(const float* dctx, const float* q, const float* k, const float* v, const float* p, float* dq,
                        float* dk_part, float* dv_part, int B, int n_tok, int F, int n_head, void* stream);
+
+/*
+ * ContentVec / HuBERT content encoder (serenade_amd/contentvec.py; the `hubert` track of serenade/bin/preprocess.py:
+ * 41-50,361-368,495-503, transformers HubertModel with the last feature-conv stride set to 1).  The rest of the encoder
+ * is srn_conv_gemm (feature convs 1-6 and the feed-forward with SRN_POST_GELU), srn_layernorm and srn_softmax_rows.
+ */
+/* rows of the partial-sum chunks srn_cvec_conv0 writes per item for T0 frames */
+int srn_frame_stats_chunks(int T);
+/* Feature-conv layer 0 (Cin = 1, k <= 16, any stride, no bias): wave (B, n) at row stride wave_bs (samples at or past n
+ * read as zero), w (C, k) -> out (B, T0, C) channels-last, out[b][t][c] = sum_j w[c][j] wave[b][t stride + j] for
+ * t < lens[b] and 0 beyond.  partials (B, srn_frame_stats_chunks(T0), C, 2) float64: per chunk (sum, sumsq) of the
+ * valid frames, for srn_channel_norm_gelu. */
+int srn_cvec_conv0(const float* wave, int64_t wave_bs, int n, const int32_t* lens, const float* w, float* out,
+                   double* partials, int B, int T0, int C, int k, int stride, void* stream);
+/* GroupNorm(num_groups = C) over each item's valid frames t < lens[b] (statistics from srn_cvec_conv0's partials, fp64),
+ * affine, GELU:  y = GELU((x - mean) / sqrt(var + eps) * gamma + beta) on valid rows, 0 on padded rows.  x, y (B, T, C)
+ * (y may be x); stats (B, C, 2) receives (mean, rstd). */
+int srn_channel_norm_gelu(const float* x, const double* partials, int n_chunks, const int32_t* lens,
+                          const float* gamma, const float* beta, float* stats, float* y, int B, int T, int C, float eps,
+                          void* stream);
+/* Positional conv of the encoder (HubertPositionalConvEmbedding + HubertSamePadLayer) with its GELU and residual:
+ *   y[b][t][n] = x[b][t][n] + GELU(bias[n] + sum_{j < k, c < Cg} w[g][j][c][n - g Cg] x[b][t + j - pad][g Cg + c])
+ * g = n / Cg, Cg = C / groups (a multiple of 4, <= 64), k <= 128; rows outside [0, min(lens[b], T)) read as zero (lens
+ * may be NULL).  w is packed [groups][k][Cg][Cg <= 32 ? 32 : 64] (zero columns past Cg).  x, y (B, T, C), y != x.
+ * Exact fp32 (v_mfma_f32_32x32x2_f32). */
+int srn_posconv_gelu_res(const float* x, const int32_t* lens, const float* w, const float* bias, float* y, int B,
+                         int T, int C, int groups, int k, int pad, void* stream);
 
 #ifdef __cplusplus
 }

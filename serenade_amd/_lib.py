@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("SERENADE_AMD_LIB") or os.path.join(_HERE, "libserenad
 SRN_MAX_TAPS = 16
 ACT_NONE, ACT_LEAKY, ACT_SILU, ACT_MISH = 0, 1, 2, 3
 RES_NONE, RES_ADD, RES_AXPY = 0, 1, 2
-POST_NONE, POST_DIV, POST_TANH, POST_RELU, POST_LEAKY = 0, 1, 2, 3, 4
+POST_NONE, POST_DIV, POST_TANH, POST_RELU, POST_LEAKY, POST_GELU = 0, 1, 2, 3, 4, 5
 PREC_FP32, PREC_BF16X3, PREC_BF16X6 = 0, 1, 2
 # SrnConvParams.route (testing / A-B timing): which kernels srn_conv_gemm may choose from
 ROUTE_AUTO, ROUTE_TILED, ROUTE_HALO, ROUTE_GENERIC, ROUTE_STRIP, ROUTE_FAST_FP32 = 0, 1, 2, 3, 4, 5
@@ -175,6 +175,10 @@ _SIGS = {
     "srn_f0_match_length": (c_int, [_P, c_int64, _P, _P, c_int64, _P, c_int, c_int, _P]),
     "srn_cont_f0": (c_int, [_P, c_int64, _P, _P, _P, _P, c_int, _P]),
     "srn_sifigan_excitation": (c_int, [POINTER(SrnExcitationParams), _P]),
+    "srn_frame_stats_chunks": (c_int, [c_int]),
+    "srn_cvec_conv0": (c_int, [_P, c_int64, c_int, _P, _P, _P, _P] + [c_int] * 5 + [_P]),
+    "srn_channel_norm_gelu": (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, _P]),
+    "srn_posconv_gelu_res": (c_int, [_P] * 5 + [c_int] * 6 + [_P]),
 }
 
 EXPORTS = tuple(_SIGS)

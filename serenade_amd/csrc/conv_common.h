@@ -190,6 +190,7 @@ __device__ __forceinline__ void conv_epilogue_impl(const SrnConvParams& p, f32x1
             else if (post == SRN_POST_TANH) v = tanhf(v);
             else if (post == SRN_POST_RELU) v = fmaxf(v, 0.f);
             else if (post == SRN_POST_LEAKY) v = v > 0.f ? v : v * p.post_div;
+            else if (post == SRN_POST_GELU) v = srn_gelu_erf(v);
           }
           (o_u + dr * o_rs)[o_v] = v;
           s1 += v;

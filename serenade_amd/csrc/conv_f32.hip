@@ -167,6 +167,7 @@ __device__ __forceinline__ void f32_epilogue(const SrnConvParams& p, f32x16 (&ac
           else if (post == SRN_POST_TANH) v = tanhf(v);
           else if (post == SRN_POST_RELU) v = fmaxf(v, 0.f);
           else if (post == SRN_POST_LEAKY) v = v > 0.f ? v : v * p.post_div;
+          else if (post == SRN_POST_GELU) v = srn_gelu_erf(v);
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs_o, o_v, o_s + dr * o_rs, 0);
           s1 += v;
           s2 += v * v;

@@ -72,6 +72,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const SrnConvParams 
       else if (p.post == SRN_POST_TANH) x = tanhf(x);
       else if (p.post == SRN_POST_RELU) x = fmaxf(x, 0.f);
       else if (p.post == SRN_POST_LEAKY) x = x > 0.f ? x : x * p.post_div;
+      else if (p.post == SRN_POST_GELU) x = srn_gelu_erf(x);
       out[j] = x;
       s1 += x;
       s2 += x * x;
