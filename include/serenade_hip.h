@@ -548,6 +548,45 @@ int srn_channel_norm_gelu(const float* x, const double* partials, int n_chunks, 
 int srn_posconv_gelu_res(const float* x, const int32_t* lens, const float* w, const float* bias, float* y, int B,
                          int T, int C, int groups, int k, int pad, void* stream);
 
+/*
+ * Phoneme-informed MIDI note transcriber (serenade_amd/transcriber.py; the `est_lf0_score` track of
+ * serenade/bin/preprocess.py:374-383,506-528, TranscriptionModel of serenade/modules/phoneme_midi/model.py).  Its STFT,
+ * conv layers 1-2, flatten + Linear layers and LSTM input projections are srn_conv_gemm.  Every kernel takes per-item
+ * lengths: each item of a padded batch gets what its own B = 1 call gets.
+ */
+/* nnAudio MelSpectrogram(center=True)'s nn.ReflectionPad1d(n_fft / 2) (feature.py:7-16) of each item on its own:
+ * out (B, ld)[b][i] = x[b][reflect(i - pad)] mirrored at L = min(lens[b], n) for i < L + 2 pad, 0 beyond; x (B, n) at row
+ * stride x_bs.  Needs lens[b] > pad (checked by the caller, as ReflectionPad1d does). */
+int srn_pad_ragged(const float* x, int64_t x_bs, const int32_t* lens, float* out, int B, int n, int pad, int ld,
+                   void* stream);
+/* nnAudio mel power (mel_basis @ |X|^2) + torchaudio AmplitudeToDB("power", top_db) (feature.py:17-25):
+ * spec (B, T, ld_spec) = [re | im] of n_bins bins, mel_t (n_bins, n_mels); out (B, T, ld_out) = 10 log10(max(mel, amin))
+ * clamped below at (the item's maximum over its valid frames t < lens[b]) - top_db; frames t >= lens[b] are 0.
+ * gmax_ws: B unsigned of scratch (zeroed here by a kernel). */
+int srn_mel_db(const float* spec, int ld_spec, int n_bins, const float* mel_t, const int32_t* lens, unsigned* gmax_ws,
+               float* out, int ld_out, int B, int T, int n_mels, float amin, float top_db, void* stream);
+/* Conv-stack layer 0 (subnetworks.py:10-13,52-56): Conv2d(1 -> C, 3x3, padding (dilation, 1), dilation (dilation, 1))
+ * with BatchNorm folded into w (C, 3, 3) and bias (C), then ReLU.  x (B, T, ld_x) at item stride x_bs, F valid columns;
+ * out (B, T, F + 2, C) channels-last with a zero border column at each end of the frequency axis; frames
+ * t >= lens[b] read and write as zero.  dilation 1 or 2. */
+int srn_trans_conv0(const float* x, int64_t x_bs, int ld_x, const int32_t* lens, const float* w, const float* bias,
+                    float* out, int B, int T, int F, int C, int dilation, void* stream);
+/* MaxPool2d((1, 2)) (subnetworks.py:20,27) on in (B, T, F_in + 2, C) bordered.  flatten 0: out (B, T, F_in / 2 + 2, C)
+ * with zero border columns; flatten 1: out (B, T, ld_out), column c (F_in / 2) + f for channels c < C_valid (the
+ * transpose + flatten of subnetworks.py:36-37), zeros up to ld_out.  Frames t >= lens[b] are 0. */
+int srn_trans_pool(const float* in, const int32_t* lens, float* out, int B, int T, int F_in, int C, int C_valid,
+                   int flatten, int ld_out, void* stream);
+/* K-slices per hidden unit srn_bilstm_recur uses for H (0: H unsupported) */
+int srn_bilstm_slices(int H);
+/* Bidirectional nn.LSTM recurrence (gate order i, f, g, o; zero initial state) of BiLSTM.forward (subnetworks.py:
+ * 96-128: its 512-frame chunks with carried (h, c) equal one unchunked pass).  g (B, T, ld_g) at item stride g_bs is
+ * the input projection x W_ih^T + b_ih + b_hh, columns [0, 4H) forward and [4H, 8H) reverse; w_hh_t (2, H, H, 4):
+ * w_hh_t[d][k][j][q] = W_hh[d][q H + j][k].  The reverse direction of item b starts at t = min(lens[b], T) - 1.  out
+ * (B, T, ld_out) at item stride out_bs: columns [0, H) forward h_t, [H, 2H) reverse; rows t >= lens[b] are 0.
+ * 32 <= H <= 512, H % 8 == 0. */
+int srn_bilstm_recur(const float* g, int64_t g_bs, int ld_g, const int32_t* lens, const float* w_hh_t, float* out,
+                     int64_t out_bs, int ld_out, int B, int T, int H, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

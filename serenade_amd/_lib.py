@@ -179,6 +179,12 @@ _SIGS = {
     "srn_cvec_conv0": (c_int, [_P, c_int64, c_int, _P, _P, _P, _P] + [c_int] * 5 + [_P]),
     "srn_channel_norm_gelu": (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, _P]),
     "srn_posconv_gelu_res": (c_int, [_P] * 5 + [c_int] * 6 + [_P]),
+    "srn_pad_ragged": (c_int, [_P, c_int64, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "srn_mel_db": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, _P]),
+    "srn_trans_conv0": (c_int, [_P, c_int64, c_int, _P, _P, _P, _P] + [c_int] * 5 + [_P]),
+    "srn_trans_pool": (c_int, [_P, _P, _P] + [c_int] * 7 + [_P]),
+    "srn_bilstm_slices": (c_int, [c_int]),
+    "srn_bilstm_recur": (c_int, [_P, c_int64, c_int, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, _P]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -74,7 +74,9 @@ def _a_weight_db(freqs, min_db=-80.0):
 class _Stft:
     """reflect pad + strided implicit-GEMM STFT of (B, n) signals -> self.spec (B, frames, ld) = [re | im | 0]"""
 
-    def __init__(self, dev, B, n, n_fft, hop, win_length, pad_mode="reflect"):
+    def __init__(self, dev, B, n, n_fft, hop, win_length, pad_mode="reflect", lens=None, audio=None):
+        """lens: per-item sample counts (CUDA int32) -- each item is reflect-padded at its own end (srn_pad_ragged);
+        audio: a (B, n) buffer of the caller's to read the signal from, instead of one of the plan's own"""
         if pad_mode not in ("reflect", "constant"):
             raise ValueError(f"pad_mode {pad_mode!r}: 'reflect' or 'constant'")
         c = math.gcd(math.gcd(n_fft, hop), 16)
@@ -87,9 +89,16 @@ class _Stft:
         self.ld_sig = rows * c
         self.ld = _rup(2 * self.nb, 4)
         f = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
-        self.audio, self.sig, self.spec = f(B, n), f(B, self.ld_sig), f(B, self.frames, self.ld)
+        self.audio = f(B, n) if audio is None else audio
+        self.sig, self.spec = f(B, self.ld_sig), f(B, self.frames, self.ld)
         self.basis = torch.from_numpy(_dft_basis(n_fft, win_length, self.ld)).to(dev)
-        self.ops = [ops.CallOp("srn_pad_signal", (self.audio, self.sig, B, n, pad, self.ld_sig, int(pad_mode == "constant")))]
+        if lens is None:
+            self.ops = [ops.CallOp("srn_pad_signal", (self.audio, self.sig, B, n, pad, self.ld_sig,
+                                                      int(pad_mode == "constant")))]
+        else:
+            if pad_mode != "reflect":
+                raise ValueError("per-item lengths need pad_mode 'reflect'")
+            self.ops = [ops.CallOp("srn_pad_ragged", (self.audio, n, lens, self.sig, B, n, pad, self.ld_sig))]
         # A frame is a contraction over n_fft samples = taps of `cw` samples each.  The signal is viewed as rows that START
         # every c samples (row stride c, so any frame start is a row) but are cw = 32 samples WIDE (overlapping rows are
         # fine for a read-only operand): 32-channel taps take the fast contraction kernel, 16-wide ones the generic one
