@@ -587,6 +587,46 @@ int srn_bilstm_slices(int H);
 int srn_bilstm_recur(const float* g, int64_t g_bs, int ld_g, const int32_t* lens, const float* w_hh_t, float* out,
                      int64_t out_bs, int ld_out, int B, int T, int H, void* stream);
 
+/*
+ * pYIN F0 estimation, librosa 0.10 `librosa.pyin` (serenade_amd/pitch.py): the f0 contour that the transcriber's
+ * FramewiseDecoder.decode turns into note pitches (serenade/modules/phoneme_midi/decoding.py:36-45,
+ * librosa.pyin(audio, fmin=65, fmax=2093, sr, frame_length=win_length, hop_length, center=True)).  fp64; the step
+ * numbers are those of tests/_pyin_ref.py, the restatement both entry points are held to.  Every item of a padded
+ * batch gets what its own B = 1 call gets.  Limits: frame_length <= SRN_PYIN_MAX_FRAME, 3 <= max_period - min_period
+ * + 1 <= SRN_PYIN_MAX_PERIODS, 2 n_bins <= SRN_PYIN_MAX_STATES, n_thresholds <= SRN_PYIN_MAX_THRESHOLDS.
+ */
+#define SRN_PYIN_MAX_FRAME 4096
+#define SRN_PYIN_MAX_PERIODS 1024
+#define SRN_PYIN_MAX_STATES 4096
+#define SRN_PYIN_MAX_THRESHOLDS 1024
+/* Steps 1-5 (decoding.py:36-45 -> librosa.pyin up to the observation matrix), one workgroup per (item, frame).
+ * x (B, N) float32 at row stride x_bs, lens[b] <= N valid samples, frames[b] <= T frames of item b (frame t starts at
+ * sample t hop_length - pad; samples outside [0, lens[b]) read as zero).  Per frame: the cumulative mean normalised
+ * difference over periods [min_period, max_period] (window win_length), parabolic shifts, troughs, their probabilities
+ * (thresholds, beta_probs: n_thresholds; boltz_fact[c] = (1 - e^-l) / (1 - e^-l c) for c <= nf, boltz_exp[p] = e^-l p
+ * for p < nf, no_trough[m] = no_trough_prob * sum(beta_probs[:m]) for m <= n_thresholds; nf = max_period - min_period
+ * + 1), and the pitch bins round(bins_per_octave log2(sr / period / fmin)) clipped to [0, n_bins].  Writes obs
+ * (B, T, n_bins): the voiced observation row (the larger period wins a shared bin) and voiced_prob (B, T), clipped to
+ * [0, 1]; frames t >= frames[b] get voiced_prob 0 and leave obs untouched. */
+int srn_pyin_observe(const float* x, int64_t x_bs, const int32_t* lens, const int32_t* frames, const double* thresholds,
+                     const double* beta_probs, const double* boltz_fact, const double* boltz_exp,
+                     const double* no_trough, double* obs, double* voiced_prob, int B, int N, int T, int frame_length,
+                     int win_length, int hop_length, int pad, int min_period, int max_period, int n_thresholds,
+                     double sr, double fmin, double bins_per_octave, int n_bins, void* stream);
+/* Steps 6-8 (decoding.py:36-45 -> librosa.sequence.viterbi and pyin's state -> f0 map), one workgroup per item over
+ * its own frames[b] frames.  States 0 .. n_bins - 1 voiced, n_bins .. 2 n_bins - 1 unvoiced; observations: obs (the
+ * voiced row) and (1 - voiced_prob) / n_bins on every unvoiced state, log(p + tiny), log_tiny where p = 0.  log_band
+ * (2, width, n_bins): [0][d + width / 2][q] = log((1 - switch) T[q + d][q] + tiny), [1] the same with the switch
+ * probability (T = transition_local(n_bins, width, "triangle")); log(tiny) = log_tiny everywhere else, as the dense
+ * matrix has it.  log_p_init (2 n_bins).  The argmax is the first maximal predecessor, as librosa's.  ptr_ws: B T 2 n_bins
+ * uint16 of scratch.  Writes states (B, T) int32 (-1 past frames[b]), f0 (B, T): freqs[state] (freqs has 2 n_bins
+ * entries, the unvoiced half repeating the voiced one), fill_na on unvoiced states when fill_unvoiced and on frames past
+ * frames[b]; voiced_flag (B, T) 0/1. */
+int srn_pyin_viterbi(const double* obs, const double* voiced_prob, const int32_t* frames, const double* log_band,
+                     const double* log_p_init, const double* freqs, double log_tiny, double fill_na, int fill_unvoiced,
+                     uint16_t* ptr_ws, int32_t* states, double* f0, uint8_t* voiced_flag, int B, int T, int n_bins,
+                     int width, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

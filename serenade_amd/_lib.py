@@ -185,6 +185,8 @@ _SIGS = {
     "srn_trans_pool": (c_int, [_P, _P, _P] + [c_int] * 7 + [_P]),
     "srn_bilstm_slices": (c_int, [c_int]),
     "srn_bilstm_recur": (c_int, [_P, c_int64, c_int, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, _P]),
+    "srn_pyin_observe": (c_int, [_P, c_int64] + [_P] * 9 + [c_int] * 10 + [c_double] * 3 + [c_int, _P]),
+    "srn_pyin_viterbi": (c_int, [_P] * 6 + [c_double] * 2 + [c_int] + [_P] * 4 + [c_int] * 4 + [_P]),
 }
 
 EXPORTS = tuple(_SIGS)

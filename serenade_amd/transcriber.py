@@ -9,6 +9,8 @@ FramewiseDecoder (decoding.py) on the host.
       .forward(wave16k, lengths)        (B, T, 3) onset / offset / activation logits of every item on its own
       .frames(n_samples)                T = 1 + n // hop_length
     FramewiseDecoder(config).decode(logits_item, f0)      decoding.py, on the host
+    reference_f0(wave16k, lengths, config)                decoding.py:36-45's librosa.pyin call, on the GPU
+                                                          (pitch.pyin): one f0 contour per item for decode(f0=...)
     estimate_score(pitches, intervals, n_samples, ...)    preprocess.py:510-528: (midi frames, est_lf0_score)
 
 The network, per item (B = 1, eval mode):
@@ -40,12 +42,12 @@ import copy
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, pitch
 from .features import _slaney_mel, _Stft
 from .models import _lru_get, _rup
 from .ops import ConvOp, GraphRunner
 
-__all__ = ["TranscriptionModel", "FramewiseDecoder", "estimate_score", "DEFAULT_CONFIG"]
+__all__ = ["TranscriptionModel", "FramewiseDecoder", "estimate_score", "reference_f0", "DEFAULT_CONFIG"]
 
 # ASSUMED geometry: no transcriber checkpoint is available to read ckpt["config"] from.  The front-end follows the
 # reference's 16 kHz input (preprocess.py:495,506); model_complexity 48 (model_size 768, LSTM hidden 384) and the
@@ -493,6 +495,20 @@ class FramewiseDecoder:
         win[nan] = 0
         win /= win.sum()
         return weighted_median(seg.cpu().numpy(), win.cpu().numpy())
+
+
+def reference_f0(wave16k, lengths=None, config=None):
+    """the f0 contours FramewiseDecoder.decode(pred, audio=x) computes with librosa (decoding.py:36-45:
+    librosa.pyin(audio, fmin=65, fmax=2093, sr, frame_length=win_length, hop_length, fill_na=nan, center=True)), for
+    every item of wave16k (B, N) or (N,) on the GPU (pitch.pyin).  A list of numpy float64 contours, one per item over
+    its own frames (NaN where unvoiced), each ready for decode(logits, f0=...)."""
+    cfg = DEFAULT_CONFIG if config is None else config
+    x = wave16k.reshape(1, -1) if wave16k.ndim == 1 else wave16k
+    f0, _, _, frames = pitch.pyin(x, lengths, fmin=65, fmax=2093, sr=cfg["sample_rate"],
+                                  frame_length=cfg["win_length"], hop_length=cfg["hop_length"], fill_na=np.nan,
+                                  center=True)
+    f0 = f0.cpu().numpy()
+    return [f0[b, :int(n)].copy() for b, n in enumerate(frames)]
 
 
 def midi_to_frames(midi_values, time_intervals, T, shift_ms=10):

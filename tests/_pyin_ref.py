@@ -1,0 +1,193 @@
+"""float64 numpy + scipy restatement of librosa 0.10.x `librosa.pyin` (librosa/core/pitch.py, librosa/sequence.py):
+the contract serenade_amd/pitch.py and serenade_amd/csrc/pyin.hip are tested against.  librosa is not installed where
+this project is tested, so this file is the pin ("parity unpinned", like the log-mel row).
+
+Where librosa leaves an order of operations to a library, it is pinned here, and pyin.hip follows it:
+  - the autocorrelation is a direct sum over j = 1 .. W in ascending j (librosa: an FFT; both are the same
+    sum, rounded differently);
+  - the threshold sum of the trough prior and the voiced-probability sum are sequential (librosa: BLAS dot, np.sum);
+  - the input is converted to float64 first (librosa keeps a float32 input's framing and energy in float32).
+The rest is librosa's own arithmetic, step for step.
+"""
+import numpy as np
+import scipy.signal
+import scipy.stats
+
+TINY = np.finfo(np.float64).tiny
+
+
+def geometry(*, fmin, fmax, sr=22050, frame_length=2048, win_length=None, hop_length=None, resolution=0.1,
+             max_transition_rate=35.92):
+    """the derived sizes of one pyin call"""
+    if win_length is None:
+        win_length = frame_length // 2
+    if hop_length is None:
+        hop_length = frame_length // 4
+    min_period = int(np.floor(sr / fmax))
+    max_period = min(int(np.ceil(sr / fmin)), frame_length - win_length - 1)
+    nbps = int(np.ceil(1.0 / resolution))
+    n_bins = int(np.floor(12 * nbps * np.log2(fmax / fmin))) + 1
+    width = round(max_transition_rate * 12 * hop_length / sr) * nbps + 1
+    return dict(win_length=win_length, hop_length=hop_length, min_period=min_period, max_period=max_period,
+                nbps=nbps, n_bins=n_bins, width=width)
+
+
+def transition_local(n_states, width):
+    """librosa.sequence.transition_local(n_states, width, window="triangle", wrap=False)"""
+    transition = np.zeros((n_states, n_states), dtype=np.float64)
+    win = scipy.signal.get_window("triang", width, fftbins=False)
+    lpad = (n_states - width) // 2
+    for i in range(n_states):
+        row = np.pad(win, (lpad, n_states - width - lpad))
+        row = np.roll(row, n_states // 2 + i + 1)
+        row[min(n_states, i + width // 2 + 1):] = 0
+        row[:max(0, i - width // 2)] = 0
+        transition[i] = row
+    transition /= transition.sum(axis=1, keepdims=True)
+    return transition
+
+
+def transition_loop(n_states, prob):
+    """librosa.sequence.transition_loop with one self-loop probability"""
+    t = np.empty((n_states, n_states), dtype=np.float64)
+    for i in range(n_states):
+        t[i] = (1.0 - prob) / (n_states - 1)
+        t[i, i] = prob
+    return t
+
+
+def transition(n_bins, width, switch_prob):
+    return np.kron(transition_loop(2, 1 - switch_prob), transition_local(n_bins, width))
+
+
+def frames_of(y, frame_length, hop_length, center=True):
+    """the centred (constant-padded) frames of a 1-D signal, float64, (T, frame_length)"""
+    y = np.asarray(y, dtype=np.float64)
+    if center:
+        y = np.pad(y, (frame_length // 2, frame_length // 2))
+    n = 1 + (len(y) - frame_length) // hop_length
+    idx = np.arange(frame_length)[None, :] + hop_length * np.arange(n)[:, None]
+    return y[idx]
+
+
+def cmnd(frames, win_length, min_period, max_period):
+    """cumulative mean normalised difference of each frame, (T, max_period - min_period + 1)"""
+    W = win_length
+    out = np.empty((frames.shape[0], max_period - min_period + 1))
+    for t, y in enumerate(frames):
+        tau = np.arange(1, max_period + 1)
+        prod = y[None, 1:W + 1] * y[tau[:, None] + np.arange(1, W + 1)[None, :]]
+        acf = np.concatenate([[0.0], np.cumsum(prod, axis=1)[:, -1]])
+        acf[np.abs(acf) < 1e-6] = 0
+        c = np.cumsum(y * y)
+        e = c[W:W + max_period + 1] - c[:max_period + 1]
+        e[np.abs(e) < 1e-6] = 0
+        d = e[:1] + e - 2 * acf
+        cm = np.cumsum(d[1:max_period + 1]) / np.arange(1, max_period + 1)
+        out[t] = d[min_period:max_period + 1] / (cm[min_period - 1:max_period] + TINY)
+    return out
+
+
+def parabolic_shift(x):
+    """librosa 0.10 _parabolic_interpolation of one frame"""
+    s = np.zeros_like(x)
+    for i in range(1, len(x) - 1):
+        a = x[i + 1] + x[i - 1] - 2 * x[i]
+        b = (x[i + 1] - x[i - 1]) / 2
+        s[i] = 0.0 if np.abs(b) >= np.abs(a) else -b / a
+    return s
+
+
+def troughs(x):
+    """util.localmin with edge padding, then pyin's is_trough[0] = x[0] < x[1]"""
+    xp = np.pad(x, 1, mode="edge")
+    t = (x < xp[:-2]) & (x <= xp[2:])
+    t[0] = x[0] < x[1]
+    return t
+
+
+def prior_tables(n_thresholds=100, beta_parameters=(2, 18), no_trough_prob=0.01):
+    thresholds = np.linspace(0, 1, n_thresholds + 1)
+    beta_probs = np.diff(scipy.stats.beta.cdf(thresholds, beta_parameters[0], beta_parameters[1]))
+    return thresholds[1:], beta_probs
+
+
+def observe_frame(x, shift, g, sr, fmin, thresholds, beta_probs, boltzmann_parameter=2, no_trough_prob=0.01):
+    """one frame's voiced observations (n_bins,), voiced probability, and whether a trough height or a localmin
+    comparison lies within 1e-12 of its threshold or neighbour"""
+    n_bins = g["n_bins"]
+    obs = np.zeros(n_bins + 1)
+    dx = np.abs(np.diff(x))
+    near = bool((dx < 1e-12).any())
+    is_t = troughs(x)
+    (ti,) = np.nonzero(is_t)
+    if len(ti):
+        h = x[ti]
+        near = near or bool((np.abs(h[:, None] - thresholds[None, :]) < 1e-12).any())
+        below = np.less.outer(h, thresholds)
+        pos = np.cumsum(below, axis=0) - 1
+        cnt = np.count_nonzero(below, axis=0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            prior = scipy.stats.boltzmann.pmf(pos, boltzmann_parameter, cnt)
+        prior[~below] = 0
+        probs = np.cumsum(prior * beta_probs, axis=1)[:, -1]
+        gm = np.argmin(h)
+        m = np.count_nonzero(~below[gm, :])
+        probs[gm] += no_trough_prob * np.sum(beta_probs[:m])
+        keep = probs != 0
+        i = ti[keep]
+        period = (g["min_period"] + i) + shift[i]
+        f0 = sr / period
+        b = np.clip(np.round(12 * g["nbps"] * np.log2(f0 / fmin)), 0, n_bins).astype(int)
+        obs[b] = probs[keep]  # ascending period: the larger period wins a shared bin
+    vp = min(max(np.cumsum(obs[:n_bins])[-1], 0.0), 1.0)
+    return obs[:n_bins], vp, near
+
+
+def viterbi(prob, trans, p_init):
+    """librosa.sequence.viterbi on prob (T, S): dense, log domain, first argmax; the state path (T,)"""
+    log_trans = np.log(trans + TINY)
+    log_prob = np.log(prob + TINY)
+    value = log_prob[0] + np.log(p_init + TINY)
+    T, S = prob.shape
+    ptr = np.zeros((T, S), dtype=np.int64)
+    for t in range(1, T):
+        m = value[:, None] + log_trans
+        ptr[t] = np.argmax(m, axis=0)
+        value = log_prob[t] + m[ptr[t], np.arange(S)]
+    state = np.zeros(T, dtype=np.int64)
+    state[-1] = np.argmax(value)
+    for t in range(T - 2, -1, -1):
+        state[t] = ptr[t + 1, state[t + 1]]
+    return state
+
+
+def obs_matrix(voiced, vp):
+    """(T, 2 n_bins) observations: the voiced half, then (1 - vp) / n_bins on every unvoiced state"""
+    T, n = voiced.shape
+    return np.concatenate([voiced, np.repeat(((1 - vp) / n)[:, None], n, axis=1)], axis=1)
+
+
+def pyin(y, *, fmin, fmax, sr=22050, frame_length=2048, win_length=None, hop_length=None, n_thresholds=100,
+         beta_parameters=(2, 18), boltzmann_parameter=2, resolution=0.1, max_transition_rate=35.92, switch_prob=0.01,
+         no_trough_prob=0.01, fill_na=np.nan, center=True):
+    """librosa.pyin of one 1-D signal -> (f0, voiced_flag, voiced_prob, near_tie) with near_tie per frame"""
+    g = geometry(fmin=fmin, fmax=fmax, sr=sr, frame_length=frame_length, win_length=win_length,
+                 hop_length=hop_length, resolution=resolution, max_transition_rate=max_transition_rate)
+    fr = frames_of(y, frame_length, g["hop_length"], center)
+    yin = cmnd(fr, g["win_length"], g["min_period"], g["max_period"])
+    thresholds, beta_probs = prior_tables(n_thresholds, beta_parameters, no_trough_prob)
+    T, n = len(fr), g["n_bins"]
+    voiced, vp, near = np.zeros((T, n)), np.zeros(T), np.zeros(T, dtype=bool)
+    for t in range(T):
+        voiced[t], vp[t], near[t] = observe_frame(yin[t], parabolic_shift(yin[t]), g, sr, fmin, thresholds,
+                                                  beta_probs, boltzmann_parameter, no_trough_prob)
+    p_init = np.zeros(2 * n)
+    p_init[n:] = 1 / n
+    states = viterbi(obs_matrix(voiced, vp), transition(n, g["width"], switch_prob), p_init)
+    freqs = fmin * 2 ** (np.arange(n) / (12 * g["nbps"]))
+    f0 = freqs[states % n]
+    flag = states < n
+    if fill_na is not None:
+        f0[~flag] = fill_na
+    return f0, flag, vp, near
