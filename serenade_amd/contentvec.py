@@ -26,8 +26,8 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .models import S_BUDGET, _lru_get, _rup, attention_chunks
 from .ops import ConvOp, GraphRunner
+from .plan import attention_ops, attention_scores, check_state, linear_op, lru_get, rup, wave_batch
 
 __all__ = ["ContentVec", "extract_hubert", "DEFAULT_CONFIG"]
 
@@ -133,13 +133,7 @@ class ContentVec:
     def load_state_dict(self, sd):
         s = self.map_state_dict(sd)
         want = self.state_shapes()
-        missing = [k for k in want if k not in s]
-        unexpected = sorted(set(s) - set(want))
-        if missing or unexpected:
-            raise KeyError(f"ContentVec.load_state_dict: missing {missing[:8]}, unexpected {unexpected[:8]}")
-        for k, shp in want.items():
-            if tuple(s[k].shape) != shp:
-                raise ValueError(f"ContentVec.load_state_dict: {k} has shape {tuple(s[k].shape)}, expected {shp}")
+        check_state("ContentVec.load_state_dict", s, want)
         c = self.config
         C, D = c["conv_dim"][0], c["hidden_size"]
         G, K = c["num_conv_pos_embedding_groups"], c["num_conv_pos_embeddings"]
@@ -196,26 +190,12 @@ class ContentVec:
         item's count are padding (unspecified values)."""
         if self.w is None:
             raise RuntimeError("ContentVec: load_state_dict first")
-        if not isinstance(wave16k, torch.Tensor):
-            wave16k = torch.as_tensor(np.asarray(wave16k, dtype=np.float32))
-        a = wave16k.detach()
-        if a.dim() == 1:
-            a = a.unsqueeze(0)
-        if a.dim() != 2:
-            raise ValueError("ContentVec: wave16k must be (n,) or (B, n)")
-        if not a.is_cuda:
-            if self.device.type != "cuda":
-                raise RuntimeError("ContentVec needs a CUDA (ROCm) device; there is no CPU fallback")
-            a = a.to(self.device)
-        a = a.to(torch.float32)
+        a, lens = wave_batch(wave16k, lengths, self.device, "ContentVec")
         B, n = a.shape
-        lens = [n] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-        if len(lens) != B or max(lens) > n or min(lens) < 1:
-            raise ValueError(f"ContentVec: lengths {lens} do not fit a batch of {B} x {n} samples")
         if min(self.frames(v) for v in lens) < 1:
             raise ValueError(f"ContentVec: an utterance of {min(lens)} samples is shorter than one output frame")
         key = (str(a.device), B, n, tuple(lens))
-        plan = _lru_get(self._plans, key, 8, lambda: _Plan(self, a.device, B, n, lens))
+        plan = lru_get(self._plans, key, 8, lambda: _Plan(self, a.device, B, n, lens))
         plan.wave.copy_(a, non_blocking=True)
         plan.run()
         out = plan.out.clone()
@@ -265,23 +245,19 @@ class _Plan:
         xn = f(B, T, C)
         ol.append(ops.layernorm_op(cur, w["fp_ln_w"], w["fp_ln_b"], xn, B * T, C, eps))
         hA, hB = f(B, T, D), f(B, T, D)
-
-        def lin(inp, K, wt, b, out, N, **kw):
-            return ConvOp(in0=inp, w=wt, out=out, n_batch=1, T_in=B * T, T_out=B * T, C_in=K, N=N, ld_in0=K, ldw=K,
-                          ld_out=N, bias=b, precision=_lib.PREC_FP32, **kw)
-
-        ol.append(lin(xn, C, w["fp_w"], w["fp_b"], hA, D))
+        fp32 = _lib.PREC_FP32
+        ol.append(linear_op(xn, B * T, C, w["fp_w"], w["fp_b"], hA, D, precision=fp32))
         # ---- h + GELU(posconv(h)) (rows past an item's length read as zero), then the encoder's LayerNorm
         K = c["num_conv_pos_embeddings"]
         ol.append(ops.CallOp("srn_posconv_gelu_res", (hA, self.lens[-1], w["pos_w"], w["pos_b"], hB, B, T, D,
                                                       c["num_conv_pos_embedding_groups"], K, K // 2)))
         X = hA
         ol.append(ops.layernorm_op(hB, w["enc_ln_w"], w["enc_ln_b"], X, B * T, D, eps))
-        # ---- post-LN transformer layers (DecoderPlan.tfm's attention: chunked S, V^T from the QKV epilogue)
-        Tp = _rup(T, 32)
+        # ---- post-LN transformer layers (plan.attention_ops: chunked S, V^T from the QKV epilogue)
+        Tp = rup(T, 32)
         qkv = f(B, T, 3 * D)
-        Vt = f(B, D, Tp)
-        S = f(max(1, min(B * H, S_BUDGET // (T * Tp * 4))) * T * Tp)
+        Vt = f(B, D, Tp)  # zeroed: the pad columns are never written and must be zero
+        S = attention_scores(B, H, T, dev)
         O, G = f(B, T, D), f(B, T, FF)
         ln = self.lens[-1]
         prec = ops.attention_precision()
@@ -289,26 +265,17 @@ class _Plan:
             ol.append(ConvOp(in0=X, w=t["qkv_w"], out=qkv, n_batch=B, T_in=T, T_out=T, C_in=D, N=3 * D, in0_bs=T * D,
                              ld_in0=D, ldw=D, out_bs=T * 3 * D, ld_out=3 * D, bias=t["qkv_b"], out_tr=Vt,
                              out_tr_col0=2 * D, out_tr_bs=D * Tp, ld_out_tr=Tp, precision=_lib.PREC_FP32))
-            for b0, nb, h0_, nh in attention_chunks(B, H, T * Tp * 4, S.numel() * 4):
-                q_off = b0 * T * 3 * D + h0_ * hd
-                ol.append(ConvOp(in0=(qkv, q_off), w=(qkv, q_off + D), out=S, n_batch=nb, n_head=nh, T_in=T, T_out=T,
-                                 C_in=hd, N=T, in0_bs=T * 3 * D, in0_hs=hd, ld_in0=3 * D, w_bs=T * 3 * D, w_hs=hd,
-                                 ldw=3 * D, out_bs=nh * T * Tp, out_hs=T * Tp, ld_out=Tp, alpha=1.0 / math.sqrt(hd),
-                                 precision=prec))
-                ol.append(ops.softmax_rows_op(S, (ln, b0), nb * nh, nh, T, Tp))
-                ol.append(ConvOp(in0=S, w=(Vt, b0 * D * Tp + h0_ * hd * Tp), out=(O, b0 * T * D + h0_ * hd), n_batch=nb,
-                                 n_head=nh, T_in=T, T_out=T, C_in=Tp, N=hd, in0_bs=nh * T * Tp, in0_hs=T * Tp,
-                                 ld_in0=Tp, w_bs=D * Tp, w_hs=hd * Tp, ldw=Tp, out_bs=T * D, out_hs=hd, ld_out=D,
-                                 precision=prec))
-            ol.append(lin(O, D, t["o_w"], t["o_b"], hB, D, res=X, res_mode=ops.RES_ADD, ld_res=D))
+            ol += attention_ops(qkv, Vt, S, O, ln, B, H, hd, T, prec)
+            ol.append(linear_op(O, B * T, D, t["o_w"], t["o_b"], hB, D, precision=fp32, res=X, res_mode=ops.RES_ADD,
+                                ld_res=D))
             ol.append(ops.layernorm_op(hB, t["ln1_w"], t["ln1_b"], X, B * T, D, eps))
-            ol.append(lin(X, D, t["ff1_w"], t["ff1_b"], G, FF, post=_lib.POST_GELU))
-            ol.append(lin(G, FF, t["ff2_w"], t["ff2_b"], hB, D, res=X, res_mode=ops.RES_ADD, ld_res=D))
+            ol.append(linear_op(X, B * T, D, t["ff1_w"], t["ff1_b"], G, FF, precision=fp32, post=_lib.POST_GELU))
+            ol.append(linear_op(G, B * T, FF, t["ff2_w"], t["ff2_b"], hB, D, precision=fp32, res=X,
+                                res_mode=ops.RES_ADD, ld_res=D))
             ol.append(ops.layernorm_op(hB, t["ln2_w"], t["ln2_b"], X, B * T, D, eps))
         self.out = X
         self.ops = ol
         self.Ts = Ts
-        self._keep = (h0, parts, stats, bufs, xn, hA, hB, qkv, Vt, S, O, G)
         self.runner = GraphRunner(lambda: self.ops)
 
     def run(self):

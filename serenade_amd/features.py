@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .models import _lru_get, _rup
+from .plan import lru_get, require_cuda as _require_cuda, rup
 
 __all__ = ["logmelfilterbank", "loudness_extract"]
 
@@ -87,7 +87,7 @@ class _Stft:
         pad = n_fft // 2
         rows = -(-(n + 2 * pad) // c) + n_fft // c + 2  # the last frame's taps stay inside the buffer
         self.ld_sig = rows * c
-        self.ld = _rup(2 * self.nb, 4)
+        self.ld = rup(2 * self.nb, 4)
         f = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
         self.audio = f(B, n) if audio is None else audio
         self.sig, self.spec = f(B, self.ld_sig), f(B, self.frames, self.ld)
@@ -116,11 +116,6 @@ class _Stft:
 
     def load(self, audio):
         self.audio.copy_(audio.reshape(self.B, self.n), non_blocking=True)
-
-
-def _require_cuda(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"{what}: the HIP path needs CUDA (ROCm) tensors; there is no CPU fallback")
 
 
 def _as_batch(audio):
@@ -156,7 +151,7 @@ def logmelfilterbank(audio, sampling_rate, fft_size=1024, hop_size=256, win_leng
         op = ops.CallOp("srn_logmel", (st.spec, mel_t, out, B * st.frames, st.nb, st.ld, num_mels, float(eps), mode))
         return st, mel_t, out, st.ops + [op]
 
-    st, _, out, ol = _lru_get(_PLANS, key, 8, make)
+    st, _, out, ol = lru_get(_PLANS, key, 8, make)
     st.load(a)
     for op in ol:
         op()
@@ -185,7 +180,7 @@ def loudness_extract(audio, sampling_rate, hop_length, pad_mode="constant"):
         op = ops.CallOp("srn_loudness", (st.spec, aw, ws, out, B, st.frames, st.nb, st.ld, 1e-10, 80.0, 1e-5))
         return st, (aw, ws), out, st.ops + [op]
 
-    st, _, out, ol = _lru_get(_PLANS, key, 8, make)
+    st, _, out, ol = lru_get(_PLANS, key, 8, make)
     st.load(a)
     for op in ol:
         op()

@@ -15,6 +15,7 @@ The modules are weight containers plus *plans*: lists of prebuilt C-ABI calls (`
 libserenade_hip.so; torch is used for device memory, streams and the one-time weight packing.
 There is no CPU path: calling these modules with CPU tensors raises.
 """
+import functools
 import math
 
 import torch
@@ -22,6 +23,8 @@ import torch.nn as nn
 
 from . import _shapes, ops
 from .ops import ACT_LEAKY, ACT_MISH, ACT_SILU, RES_ADD, RES_AXPY, ConvOp
+from .plan import attention_ops, attention_scores, conv_op, dev_f32, linear_op, lru_get, rup, tensors_of
+from .plan import require_cuda as _require_cuda
 from .utils.masking import make_non_pad_mask
 
 __all__ = ["Serenade", "Conv1dResnet", "StyleEncoder", "CFM", "Decoder", "serenade_state_shapes"]
@@ -29,15 +32,6 @@ __all__ = ["Serenade", "Conv1dResnet", "StyleEncoder", "CFM", "Decoder", "serena
 
 def serenade_state_shapes(**params):
     return _shapes.as_meta(_shapes.serenade_shapes(**params))
-
-
-def _rup(x, m):
-    return (x + m - 1) // m * m
-
-
-def _require_cuda(t, what):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda):
-        raise RuntimeError(f"{what}: the HIP path needs CUDA (ROCm) tensors; there is no CPU fallback")
 
 
 class _Packed(nn.Module):
@@ -55,7 +49,7 @@ class _Packed(nn.Module):
 
     def _invalidate(self):
         if self._packed is not None:
-            ops.drop_weight_planes(_tensors_of(self._packed))
+            ops.drop_weight_planes(tensors_of(self._packed))
         self._packed = None
         self._plans = {}
         for m in self.children():
@@ -80,38 +74,6 @@ class _Packed(nn.Module):
         for p in self.parameters():
             return p.device
         return torch.device("cpu")
-
-
-def _dev_f32(t, dev):
-    """private fp32 device copy: packed weights never alias a live nn.Parameter, so an in-place reload of the
-    parameter (load_state_dict) cannot change -- or be missed by -- anything derived from the packed tensor"""
-    r = t.detach().to(device=dev, dtype=torch.float32).contiguous()
-    return r.clone() if r.data_ptr() == t.data_ptr() else r
-
-
-def _lru_get(cache, key, capacity, make):
-    """dict used as an LRU (insertion order = recency): a hit moves the entry to the back, a miss evicts only the
-    least recently used entries beyond `capacity` -- never the plan in use (the B = 1 decode loop sees a new length
-    with almost every utterance; GroupNorm runs over the padded length, so lengths cannot be bucketed)."""
-    if key in cache:
-        cache[key] = cache.pop(key)
-    else:
-        cache[key] = make()
-        while len(cache) > capacity:
-            cache.pop(next(iter(cache)))
-    return cache[key]
-
-
-def _tensors_of(obj):
-    """all tensors inside a nested dict / list / tuple"""
-    if isinstance(obj, torch.Tensor):
-        yield obj
-    elif isinstance(obj, dict):
-        for v in obj.values():
-            yield from _tensors_of(v)
-    elif isinstance(obj, (list, tuple)):
-        for v in obj:
-            yield from _tensors_of(v)
 
 
 def _fold_wn(sd, name):
@@ -155,9 +117,9 @@ class Decoder(_Packed):
         if self._packed is not None:
             return self._packed
         dev = self._device()
-        sd = {k: _dev_f32(v, dev) for k, v in self._own_state().items()}
+        sd = {k: dev_f32(v, dev) for k, v in self._own_state().items()}
         P = {}
-        cp0 = _rup(self.in_channels, 32)
+        cp0 = rup(self.in_channels, 32)
         P["cp0"] = cp0
         l1 = sd["time_mlp.linear_1.weight"]
         w = l1.new_zeros(l1.shape[0], cp0)
@@ -220,7 +182,7 @@ class Decoder(_Packed):
     def plan(self, B, L, n_steps, euler, per_sample_t=False, exact_ragged=False):
         key = (B, L, n_steps, bool(euler), bool(per_sample_t), bool(exact_ragged), ops.DEFAULT_PRECISION,
                ops.attention_precision())
-        return _lru_get(self._plans, key, 8,
+        return lru_get(self._plans, key, 8,
                         lambda: DecoderPlan(self, B, L, n_steps, euler, per_sample_t, exact_ragged))
 
     @torch.no_grad()
@@ -238,21 +200,6 @@ class Decoder(_Packed):
         pl.set_inputs(x, mu, speaker_features, lens, ts=ts)
         pl.run()
         return pl.read_out()
-
-
-S_BUDGET = 320 << 20  # bytes of attention scores in flight (one chunk); see DecoderPlan
-
-
-def attention_chunks(B, H, pair_bytes, budget_bytes):
-    """[(b0, n_batch, h0, n_head)] covering all (batch, head) pairs in order, each chunk's scores within the budget
-    (a single pair is always admitted): runs of whole batch items when one item's H pairs fit, else runs of heads
-    inside one batch item."""
-    fit = max(1, budget_bytes // max(pair_bytes, 1))
-    if fit >= H:
-        n = -(-B // (fit // H))  # number of chunks, then even them out
-        step = -(-B // n)
-        return [(b0, min(step, B - b0), 0, H) for b0 in range(0, B, step)]
-    return [(b, 1, h0, min(fit, H - h0)) for b in range(B) for h0 in range(0, H, fit)]
 
 
 class DecoderPlan:
@@ -304,16 +251,10 @@ class DecoderPlan:
         bufC, bufA, bufR = f(B, L, Cmax), f(B, L, Cmax), f(B, L, Cmax)
         bufN = f(B, L, Cmax)
         qkv = f(B, L, 3 * inner)
-        # Attention scores are produced and consumed in CHUNKS of (batch, head) pairs through one bounded buffer:
-        # [Q K^T -> softmax -> P V] per chunk, so S is never materialised whole -- the footprint is S_BUDGET instead of
-        # B * H * L^2 * 4 B (50 GiB at B=32 x T=4096 before) -- and a chunk stays inside the 256 MiB Infinity Cache
-        # between its three kernels.  A chunk is a run of whole batch items, or a run of heads of one batch item.
-        Lp = _rup(L, 32)
-        per_pair = L * Lp * 4
-        S = torch.empty(max(1, min(B * H, S_BUDGET // per_pair)) * L * Lp, device=dev, dtype=torch.float32)
+        self.S = S = attention_scores(B, H, L, dev)  # one bounded buffer for every resolution (tools/footprint.py)
         # V^T per resolution, (B, inner, rup(T, 32)): P.V then contracts k-major rows like every other GEMM.  The pad
         # columns are never written (zeros from allocation) and meet exact zeros of the softmax.
-        Vt = {T: f(B, inner, _rup(T, 32)) for T in sorted(set(Ts))}
+        Vt = {T: f(B, inner, rup(T, 32)) for T in sorted(set(Ts))}
         bufO = f(B, L, inner)
         ffh = max(t["ff2_w"].shape[1] for t in P["tfm"])
         bufG = f(B, L, ffh)
@@ -321,22 +262,16 @@ class DecoderPlan:
         gnp = f(B, (L + 31) // 32, Cmax // 32, 2)
         self.dphi = f(B, L, oc) if not euler else None
         self.out_ct = f(B, oc, L)
-        self._keep = (bufX, bufY, bufC, bufA, bufR, bufN, qkv, S, Vt, bufO, bufG, hid, gnp)
 
         # ---- once-per-solve conditioning ops (time embedding for all steps, speaker affine)
         tdim = dec.in_channels
         pre = [ops.sinusoidal_emb_op(self.t_dev, self.sin, n_steps, tdim, cp0)]
-
-        def lin(a, M, K, w, b, out, N, **kw):
-            return ConvOp(in0=a, w=w, out=out, n_batch=1, T_in=M, T_out=M, C_in=K, N=N, ld_in0=K, ldw=w.shape[1],
-                          ld_out=N, bias=b, **kw)
-
-        pre.append(lin(self.sin, n_steps, cp0, P["t1_w"], P["t1_b"], self.e1, self.e1.shape[1]))
-        pre.append(lin(self.e1, n_steps, self.e1.shape[1], P["t2_w"], P["t2_b"], self.temb, self.temb.shape[1],
-                       pro_act=ACT_SILU))
-        pre.append(lin(self.temb, n_steps, self.temb.shape[1], P["tb_w"], P["tb_b"], self.tb, self.tb.shape[1],
-                       pro_act=ACT_MISH))
-        pre.append(lin(self.spk, B, dec.spk_embed_dim, P["spk_w"], P["spk_b"], self.ss, self.ss.shape[1]))
+        pre.append(linear_op(self.sin, n_steps, cp0, P["t1_w"], P["t1_b"], self.e1, self.e1.shape[1]))
+        pre.append(linear_op(self.e1, n_steps, self.e1.shape[1], P["t2_w"], P["t2_b"], self.temb, self.temb.shape[1],
+                             pro_act=ACT_SILU))
+        pre.append(linear_op(self.temb, n_steps, self.temb.shape[1], P["tb_w"], P["tb_b"], self.tb, self.tb.shape[1],
+                             pro_act=ACT_MISH))
+        pre.append(linear_op(self.spk, B, dec.spk_embed_dim, P["spk_w"], P["spk_b"], self.ss, self.ss.shape[1]))
         self.pre = pre
 
         tb_ld = self.tb.shape[1]
@@ -349,11 +284,7 @@ class DecoderPlan:
             o1 += r["cout"]
             o2 += 2 * r["cout"]
 
-        def conv(inp, cin, T_in, w, b, out, cout, T_out, taps, ld_in=None, **kw):
-            ld_in = cin if ld_in is None else ld_in
-            return ConvOp(in0=inp, w=w, out=out, n_batch=B, T_in=T_in, T_out=T_out, C_in=cin, N=cout,
-                          in0_bs=T_in * ld_in, ld_in0=ld_in, ldw=w.shape[1], out_bs=kw.pop("out_bs", T_out * cout),
-                          ld_out=kw.pop("ld_out", cout), bias=b, taps=taps, **kw)
+        conv = functools.partial(conv_op, B)
 
         def resnet(ol, bi, k, lvl, xin, cin, ld_in, out, xin1=None, cin0=0):
             # the block's tail also writes LayerNorm(out) for the transformer block that follows it (tfm skips its norm1)
@@ -378,23 +309,12 @@ class DecoderPlan:
         def tfm(ol, bi, lvl, X, C):
             t = P["tfm"][bi]
             T, ln = Ts[lvl], self.lens[lvl]
-            Tp = _rup(T, 32)
+            Tp = rup(T, 32)
             # norm1(X) is already in bufN: the resnet block's tail wrote it (srn_resblock_tail_ln)
             # q | k row-major into qkv; the v third goes straight to V^T (transposed tail of the epilogue)
             ol.append(conv(bufN, C, T, t["qkv_w"], None, qkv, 3 * inner, T, [0], out_tr=Vt[T], out_tr_col0=2 * inner,
                            out_tr_bs=inner * Tp, ld_out_tr=Tp))
-            # S = Q K^T / sqrt(d) -> softmax over keys < len -> O = P V, chunk by chunk (see S above)
-            for b0, nb, h0, nh in attention_chunks(B, H, T * Tp * 4, S.numel() * 4):
-                q_off = b0 * T * 3 * inner + h0 * hd
-                ol.append(ConvOp(in0=(qkv, q_off), w=(qkv, q_off + inner), out=S, n_batch=nb, n_head=nh, T_in=T,
-                                 T_out=T, C_in=hd, N=T, in0_bs=T * 3 * inner, in0_hs=hd, ld_in0=3 * inner,
-                                 w_bs=T * 3 * inner, w_hs=hd, ldw=3 * inner, out_bs=nh * T * Tp, out_hs=T * Tp,
-                                 ld_out=Tp, alpha=1.0 / math.sqrt(hd), precision=ops.attention_precision()))
-                ol.append(ops.softmax_rows_op(S, (ln, b0), nb * nh, nh, T, Tp))
-                ol.append(ConvOp(in0=S, w=(Vt[T], b0 * inner * Tp + h0 * hd * Tp), out=(bufO, b0 * T * inner + h0 * hd),
-                                 n_batch=nb, n_head=nh, T_in=T, T_out=T, C_in=Tp, N=hd, in0_bs=nh * T * Tp,
-                                 in0_hs=T * Tp, ld_in0=Tp, w_bs=inner * Tp, w_hs=hd * Tp, ldw=Tp, out_bs=T * inner,
-                                 out_hs=hd, ld_out=inner, precision=ops.attention_precision()))
+            ol += attention_ops(qkv, Vt[T], S, bufO, ln, B, H, hd, T, ops.attention_precision())
             ol.append(conv(bufO, inner, T, t["o_w"], t["o_b"], X, C, T, [0], res=X, res_mode=RES_ADD, res_bs=T * C,
                            ld_res=C))
             ol.append(ops.layernorm_op(X, t["ln3_w"], t["ln3_b"], bufN, B * T, C))
@@ -620,7 +540,7 @@ class Conv1dResnet(_Packed):
     def packed(self):
         if self._packed is None:
             dev = self._device()
-            sd = {k: _dev_f32(v, dev) for k, v in self._own_state().items()}
+            sd = {k: dev_f32(v, dev) for k, v in self._own_state().items()}
             P = dict(in_w=ops.pack_conv_weight(_fold_wn(sd, "model.1")), in_b=sd["model.1.bias"], blocks=[])
             for n in range(self.num_layers):
                 p = f"model.{2 + n}"
@@ -643,23 +563,19 @@ class Conv1dResnet(_Packed):
         f = lambda: torch.zeros(B, T, Hd, device=dev, dtype=torch.float32)
         h, s, b1, h2 = f(), f(), f(), f()
 
-        def conv(inp, cin, w, b, o, cout, taps, **kw):
-            return ConvOp(in0=inp, w=w, out=o, n_batch=B, T_in=T, T_out=T, C_in=cin, N=cout, in0_bs=T * cin,
-                          ld_in0=cin, ldw=w.shape[1], out_bs=kw.pop("out_bs", T * cout), ld_out=kw.pop("ld_out", cout),
-                          bias=b, taps=taps, **kw)
-
+        conv = functools.partial(conv_op, B)
         rf = dict(reflect=True) if lens is None else dict(reflect=2, len_in=lens)
-        ol = [conv(x, self.in_dim, P["in_w"], P["in_b"], h, Hd, ops.conv_taps(7), **rf)]
+        ol = [conv(x, self.in_dim, T, P["in_w"], P["in_b"], h, Hd, T, ops.conv_taps(7), **rf)]
         cur, nxt = h, h2
         for blk in P["blocks"]:
             d = blk["d"]
-            ol.append(conv(cur, Hd, blk["sc_w"], blk["sc_b"], s, Hd, [0]))
-            ol.append(conv(cur, Hd, blk["c3_w"], blk["c3_b"], b1, Hd, ops.conv_taps(3, d), pro_act=ACT_LEAKY,
+            ol.append(conv(cur, Hd, T, blk["sc_w"], blk["sc_b"], s, Hd, T, [0]))
+            ol.append(conv(cur, Hd, T, blk["c3_w"], blk["c3_b"], b1, Hd, T, ops.conv_taps(3, d), pro_act=ACT_LEAKY,
                            pro_slope=0.2, **rf))
-            ol.append(conv(b1, Hd, blk["c1_w"], blk["c1_b"], nxt, Hd, [0], pro_act=ACT_LEAKY, pro_slope=0.2, res=s,
-                           res_mode=RES_ADD, res_bs=T * Hd, ld_res=Hd))
+            ol.append(conv(b1, Hd, T, blk["c1_w"], blk["c1_b"], nxt, Hd, T, [0], pro_act=ACT_LEAKY, pro_slope=0.2,
+                           res=s, res_mode=RES_ADD, res_bs=T * Hd, ld_res=Hd))
             cur, nxt = nxt, cur
-        ol.append(conv(cur, Hd, P["out_w"], P["out_b"], out, self.out_dim, ops.conv_taps(7), pro_act=ACT_LEAKY,
+        ol.append(conv(cur, Hd, T, P["out_w"], P["out_b"], out, self.out_dim, T, ops.conv_taps(7), pro_act=ACT_LEAKY,
                        pro_slope=0.2, out_bs=out_bs, ld_out=ld_out, **rf))
         return ol
 
@@ -697,7 +613,7 @@ class StyleEncoder(_Packed):
     def packed(self):
         if self._packed is None:
             dev = self._device()
-            sd = {k: (_dev_f32(v, dev) if v.is_floating_point() else v) for k, v in self._own_state().items()}
+            sd = {k: (dev_f32(v, dev) if v.is_floating_point() else v) for k, v in self._own_state().items()}
             P = dict(convs=[])
             fdim = self.idim
             for i, co in enumerate(self.chans):
@@ -707,7 +623,7 @@ class StyleEncoder(_Packed):
                 shift = sd[b + "bias"] - sd[b + "running_mean"] * scale
                 # implicit-GEMM form: BatchNorm scale folded into the weights, one [Co][kw][Ci_pad] matrix per kh
                 ci = w.shape[3]
-                cpad = _rup(ci, 4)
+                cpad = rup(ci, 4)
                 wf = w * scale.view(-1, 1, 1, 1)
                 wk = []
                 for kh in range(3):
@@ -776,8 +692,7 @@ class StyleEncoder(_Packed):
         if I % 4 != 0:
             raise ValueError(f"GRU input width {I} (mel bins left x channels) must be a multiple of 4")
         gi = torch.zeros(B, H, G3, device=dev, dtype=torch.float32)
-        ol.append(ConvOp(in0=cur, w=P["w_ih"], out=gi, n_batch=1, T_in=B * H, T_out=B * H, C_in=I, N=G3, ld_in0=I,
-                         ldw=I, ld_out=G3, bias=P["b_ih"]))
+        ol.append(linear_op(cur, B * H, I, P["w_ih"], P["b_ih"], gi, G3))
         ol.append(ops.gru_recur_last_op(gi, P["w_hh_t"], P["b_hh"], ref, B, H, self.gru_units))
         ol.append(ops.style_token_attention_kv_op(ref, P["wq_t"], P["bq"], P["tok_k"], P["tok_v"], P["wo_t"], P["bo"],
                                                   out, B, self.gru_units, self.gst_tokens, self.gst_token_dim,
@@ -863,7 +778,7 @@ class Serenade(_Packed):
         _require_cuda(items[0][0], "Serenade.inference_ragged")
         shapes = tuple((int(it[0].shape[0]), int(it[3].shape[0])) for it in items)
         key = ("ragged", shapes, n_timesteps, ops.DEFAULT_PRECISION, ops.attention_precision())
-        rp = _lru_get(self._plans, key, 4, lambda: RaggedInferencePlan(self, shapes, n_timesteps))
+        rp = lru_get(self._plans, key, 4, lambda: RaggedInferencePlan(self, shapes, n_timesteps))
         rp.load(items)
         dev = items[0][0].device
         if noises is None:
@@ -872,7 +787,7 @@ class Serenade(_Packed):
 
     def _inference_plan(self, B, T, Tr, n_timesteps):
         key = (B, T, Tr, n_timesteps, ops.DEFAULT_PRECISION, ops.attention_precision())
-        return _lru_get(self._plans, key, 8, lambda: InferencePlan(self, B, T, Tr, n_timesteps))
+        return lru_get(self._plans, key, 8, lambda: InferencePlan(self, B, T, Tr, n_timesteps))
 
     @torch.inference_mode()
     def inference(self, x, lengths, midi, lft, ref_x, ref_lengths, ref_logmel, ref_midi, ref_lft,

@@ -3,6 +3,10 @@
 Tensors are torch CUDA fp32 tensors used as device memory only; every wrapper passes raw
 pointers, sizes and the current HIP stream.  All activations are channels-last (B, T, C).
 Nothing here computes on the host and nothing falls back to torch ops or to ``oracle/``.
+
+An op holds a reference to every tensor whose address it was built from (``ConvOp.kw``, ``ResUnitOp.kw``,
+``CallOp.targs``, ``MultiCopyOp.srcs / dst``, ``TransposeMultiOp.entries``), so a plan's buffers live exactly as long as
+its op list does: plans keep no separate list of their buffers.
 """
 import ctypes
 import os

@@ -26,7 +26,7 @@ import scipy.stats
 import torch
 
 from . import _lib
-from .models import _lru_get
+from .plan import lru_get
 
 __all__ = ["pyin", "pyin_geometry", "pyin_frames"]
 
@@ -189,7 +189,7 @@ _PLANS = {}
 
 
 def _plan(dev, B, N, lengths, key):
-    return _lru_get(_PLANS, (str(dev), B, N, lengths, key), 8, lambda: _PyinPlan(dev, B, N, lengths, key))
+    return lru_get(_PLANS, (str(dev), B, N, lengths, key), 8, lambda: _PyinPlan(dev, B, N, lengths, key))
 
 
 @torch.no_grad()

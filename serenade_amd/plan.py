@@ -1,0 +1,159 @@
+"""What every plan builder shares: the small helpers, the op builders that several plans repeat (batched conv, dense
+layer, chunked self-attention) and the input / state-dict checks of the waveform front-ends.  A plan is a list of
+prebuilt C-ABI calls (``ops.ConvOp`` / ``ops.CallOp``) over preallocated buffers; nothing here launches anything.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import ops
+from .ops import ConvOp
+
+
+def rup(x, m):
+    return (x + m - 1) // m * m
+
+
+def require_cuda(t, what):
+    """the guard in front of every entry point.  A module binds it under a name of its own (`_require_cuda`): the C-ABI
+    emulator of the CPU tests lifts the guard module by module through that name."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise RuntimeError(f"{what}: the HIP path needs CUDA (ROCm) tensors; there is no CPU fallback")
+
+
+def dev_f32(t, dev):
+    """private fp32 device copy: packed weights never alias a live nn.Parameter, so an in-place reload of the
+    parameter (load_state_dict) cannot change -- or be missed by -- anything derived from the packed tensor"""
+    r = t.detach().to(device=dev, dtype=torch.float32).contiguous()
+    return r.clone() if r.data_ptr() == t.data_ptr() else r
+
+
+def lru_get(cache, key, capacity, make):
+    """dict used as an LRU (insertion order = recency): a hit moves the entry to the back, a miss evicts only the
+    least recently used entries beyond `capacity` -- never the plan in use (the B = 1 decode loop sees a new length
+    with almost every utterance; GroupNorm runs over the padded length, so lengths cannot be bucketed)."""
+    if key in cache:
+        cache[key] = cache.pop(key)
+    else:
+        cache[key] = make()
+        while len(cache) > capacity:
+            cache.pop(next(iter(cache)))
+    return cache[key]
+
+
+def tensors_of(obj):
+    """all tensors inside a nested dict / list / tuple"""
+    if isinstance(obj, torch.Tensor):
+        yield obj
+    elif isinstance(obj, dict):
+        for v in obj.values():
+            yield from tensors_of(v)
+    elif isinstance(obj, (list, tuple)):
+        for v in obj:
+            yield from tensors_of(v)
+
+
+# ---------------------------------------------------------------------------------------------- contractions
+def conv_op(B, inp, cin, T_in, w, b, out, cout, T_out, taps, ld_in=None, **kw):
+    """Conv1d over a (B, T_in, cin) channels-last batch into (B, T_out, cout): packed weight `w`, bias `b`, input-row
+    offsets `taps`.  ld_in: row length of `inp` when it is wider than cin; out_bs / ld_out override the dense output."""
+    ld_in = cin if ld_in is None else ld_in
+    return ConvOp(in0=inp, w=w, out=out, n_batch=B, T_in=T_in, T_out=T_out, C_in=cin, N=cout,
+                  in0_bs=T_in * ld_in, ld_in0=ld_in, ldw=w.shape[1], out_bs=kw.pop("out_bs", T_out * cout),
+                  ld_out=kw.pop("ld_out", cout), bias=b, taps=taps, **kw)
+
+
+def linear_op(inp, rows, K, w, b, out, N, **kw):
+    """out (rows, N) = inp (rows, K) w^T + b, all rows of a batch as one contraction"""
+    return ConvOp(in0=inp, w=w, out=out, n_batch=1, T_in=rows, T_out=rows, C_in=K, N=N, ld_in0=K, ldw=w.shape[1],
+                  ld_out=N, bias=b, **kw)
+
+
+# ---------------------------------------------------------------------------------------------- self-attention
+S_BUDGET = 320 << 20  # bytes of attention scores in flight (one chunk); see attention_scores
+
+
+def attention_chunks(B, H, pair_bytes, budget_bytes):
+    """[(b0, n_batch, h0, n_head)] covering all (batch, head) pairs in order, each chunk's scores within the budget
+    (a single pair is always admitted): runs of whole batch items when one item's H pairs fit, else runs of heads
+    inside one batch item."""
+    fit = max(1, budget_bytes // max(pair_bytes, 1))
+    if fit >= H:
+        n = -(-B // (fit // H))  # number of chunks, then even them out
+        step = -(-B // n)
+        return [(b0, min(step, B - b0), 0, H) for b0 in range(0, B, step)]
+    return [(b, 1, h0, min(fit, H - h0)) for b in range(B) for h0 in range(0, H, fit)]
+
+
+def attention_scores(B, H, T, device):
+    """The bounded score buffer of attention_ops for sequences up to T rows.
+    Attention scores are produced and consumed in CHUNKS of (batch, head) pairs through this one buffer:
+    [Q K^T -> softmax -> P V] per chunk, so S is never materialised whole -- the footprint is S_BUDGET instead of
+    B * H * T^2 * 4 B (50 GiB at B=32 x T=4096 before) -- and a chunk stays inside the 256 MiB Infinity Cache
+    between its three kernels.  A chunk is a run of whole batch items, or a run of heads of one batch item.
+    Not zeroed: Q K^T writes every column below T of a row and srn_softmax_rows rewrites all ld columns of it, masking
+    by column < len before it looks at a value."""
+    per_pair = T * rup(T, 32) * 4
+    return torch.empty(max(1, min(B * H, S_BUDGET // per_pair)) * T * rup(T, 32), device=device, dtype=torch.float32)
+
+
+def attention_ops(qkv, Vt, S, out, lens, B, H, hd, T, precision):
+    """S = Q K^T / sqrt(d) -> softmax over keys < len -> O = P V, chunk by chunk through S (attention_scores).
+    qkv (B, T, 3 H hd): q | k row-major, as the QKV projection leaves them; Vt (B, H hd, rup(T, 32)): V^T, which that
+    projection's transposed tail wrote (P V then contracts k-major rows like every other GEMM; its pad columns must be
+    zero, they meet exact zeros of the softmax); out (B, T, H hd); lens (B,) int32 valid keys per item."""
+    inner = H * hd
+    Tp = rup(T, 32)
+    ol = []
+    for b0, nb, h0, nh in attention_chunks(B, H, T * Tp * 4, S.numel() * 4):
+        q_off = b0 * T * 3 * inner + h0 * hd
+        ol.append(ConvOp(in0=(qkv, q_off), w=(qkv, q_off + inner), out=S, n_batch=nb, n_head=nh, T_in=T,
+                         T_out=T, C_in=hd, N=T, in0_bs=T * 3 * inner, in0_hs=hd, ld_in0=3 * inner,
+                         w_bs=T * 3 * inner, w_hs=hd, ldw=3 * inner, out_bs=nh * T * Tp, out_hs=T * Tp,
+                         ld_out=Tp, alpha=1.0 / math.sqrt(hd), precision=precision))
+        ol.append(ops.softmax_rows_op(S, (lens, b0), nb * nh, nh, T, Tp))
+        ol.append(ConvOp(in0=S, w=(Vt, b0 * inner * Tp + h0 * hd * Tp), out=(out, b0 * T * inner + h0 * hd),
+                         n_batch=nb, n_head=nh, T_in=T, T_out=T, C_in=Tp, N=hd, in0_bs=nh * T * Tp,
+                         in0_hs=T * Tp, ld_in0=Tp, w_bs=inner * Tp, w_hs=hd * Tp, ldw=Tp, out_bs=T * inner,
+                         out_hs=hd, ld_out=inner, precision=precision))
+    return ol
+
+
+# ---------------------------------------------------------------------------------------------- front-end plumbing
+def wave_batch(wave, lengths, device, what, allow_channel_dim=False):
+    """(n,) or (B, n) waveform(s) -- (B, 1, n) too with allow_channel_dim -- as a tensor or numpy, and optional
+    per-item sample counts -> ((B, n) fp32 tensor on the GPU, [int lengths]).  A CPU input is uploaded to `device`."""
+    if not isinstance(wave, torch.Tensor):
+        wave = torch.as_tensor(np.asarray(wave, dtype=np.float32))
+    a = wave.detach()
+    shapes = "(n,), (B, n) or (B, 1, n)" if allow_channel_dim else "(n,) or (B, n)"
+    if allow_channel_dim and a.dim() == 3:
+        if a.shape[1] != 1:
+            raise ValueError(f"{what}: a 3-D wave must be (B, 1, n)")
+        a = a[:, 0]
+    if a.dim() == 1:
+        a = a.unsqueeze(0)
+    if a.dim() != 2:
+        raise ValueError(f"{what}: wave16k must be {shapes}")
+    if not a.is_cuda:
+        if torch.device(device).type != "cuda":
+            raise RuntimeError(f"{what} needs a CUDA (ROCm) device; there is no CPU fallback")
+        a = a.to(device)
+    a = a.to(torch.float32)
+    B, n = a.shape
+    lens = [n] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+    if len(lens) != B or max(lens) > n or min(lens) < 1:
+        raise ValueError(f"{what}: lengths {lens} do not fit a batch of {B} x {n} samples")
+    return a, lens
+
+
+def check_state(what, state, want, ignored=()):
+    """`state` must hold exactly the keys of `want` ({key: shape}) with those shapes, plus any of `ignored`"""
+    missing = [k for k in want if k not in state]
+    unexpected = sorted(set(state) - set(want) - set(ignored))
+    if missing or unexpected:
+        raise KeyError(f"{what}: missing {missing[:8]}, unexpected {unexpected[:8]}")
+    for k, shp in want.items():
+        if tuple(state[k].shape) != shp:
+            raise ValueError(f"{what}: {k} has shape {tuple(state[k].shape)}, expected {shp}")

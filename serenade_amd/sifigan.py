@@ -12,13 +12,15 @@ Mapping to kernels: every Conv1d / ConvTranspose1d phase / 1x1 conv is `srn_conv
 dilated conv gathers [x | x(t - r) | x(t + r)] rows with `srn_pd_gather` and multiplies them by [Wc | Wp | Wf] in ONE
 GEMM (K = 3C); the strided down-sampling convs use in_stride; LeakyReLUs ride in GEMM prologues / epilogues.
 """
+import functools
 from collections import OrderedDict
 
 import torch
 
 from . import _shapes, ops
-from .models import _Packed, _dev_f32, _fold_wn, _require_cuda, _rup
-from .ops import ACT_LEAKY, POST_DIV, POST_LEAKY, RES_ADD, ConvOp
+from .models import _Packed, _fold_wn
+from .ops import ACT_LEAKY, POST_DIV, POST_LEAKY, RES_ADD
+from .plan import conv_op, dev_f32, require_cuda as _require_cuda, rup
 
 DEFAULT_PARAMS = dict(
     in_channels=43, out_channels=1, channels=512, kernel_size=7, upsample_scales=(5, 4, 3, 2),
@@ -97,11 +99,11 @@ class SiFiGANGenerator(_Packed):
         if self._packed is not None:
             return self._packed
         cfg, dev = self.cfg, self._device()
-        sd = {k: _dev_f32(v, dev) for k, v in self._own_state().items()}
+        sd = {k: dev_f32(v, dev) for k, v in self._own_state().items()}
         n = len(cfg["upsample_scales"])
         sp, fp = cfg["source_network_params"], cfg["filter_network_params"]
         P = {}
-        cin_p = _rup(cfg["in_channels"], 4)
+        cin_p = rup(cfg["in_channels"], 4)
         P["cin_p"] = cin_p
         P["in_w"] = ops.pack_conv_weight(_fold_wn(sd, "input_conv"), cin_p)
         P["in_b"] = sd["input_conv.bias"]
@@ -197,11 +199,7 @@ class SiFiGANPlan:
         ol = [ops.transpose_op(self._c_in, c_cl, B, cin, T, cin * T, T, T * cin_p, cin_p),
               ops.copy_channels_op(self._x_in, Rf, 1, 0, x_cl, Rf * 4, 4, 0, B, Rf, 1)]
 
-        def conv(inp, ci, T_in, w, b, out, co, T_out, taps, **kw):
-            return ConvOp(in0=inp, w=w, out=out, n_batch=B, T_in=T_in, T_out=T_out, C_in=ci, N=co, in0_bs=T_in * ci,
-                          ld_in0=ci, ldw=w.shape[1], out_bs=kw.pop("out_bs", T_out * co), ld_out=co, bias=b, taps=taps,
-                          **kw)
-
+        conv = functools.partial(conv_op, B)
         h = f(B, T, C0)
         ol.append(conv(c_cl, cin_p, T, P["in_w"], P["in_b"], h, C0, T, ops.conv_taps(ks)))
 

@@ -30,13 +30,9 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .ops import TnGemmOp, ConvOp
+from .plan import require_cuda as _require_cuda, rup
 
 __all__ = ["Estimator", "TrainSerenade", "ParamStore", "GraphedStep", "MultiStepLR", "save_checkpoint", "load_checkpoint", "GradSync", "AdamW", "cfm_loss", "conv1d", "gn_mish", "row_ln", "attention_core", "geglu"]
-
-
-def _require_cuda(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"{what} needs the HIP library and an MI355X tensor (there is no CPU fallback)")
 
 
 def _call(name, *args):
@@ -44,10 +40,6 @@ def _call(name, *args):
 
 
 NORM_BWD_ROWS = 8  # rows per chunk of partial sums in the LayerNorm / GroupNorm backward kernels (srn_rowln_chunks, srn_gn_chunks)
-
-
-def _rup(n, m):
-    return (n + m - 1) // m * m
 
 
 # =====================================================================================================================
@@ -378,7 +370,7 @@ class _AttnCore(torch.autograd.Function):
         B, L, three = qkv.shape
         inner = three // 3
         hd = inner // H
-        Lp = _rup(L, 32)
+        Lp = rup(L, 32)
         dev = qkv.device
         alpha = 1.0 / math.sqrt(hd)
         alloc = torch.empty if Lp == L else torch.zeros  # pad columns must read as zero
@@ -451,7 +443,7 @@ class _Conv2dS2(torch.autograd.Function):
         Co, Ci = w.shape[0], w.shape[1]
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         dev = x.device
-        K = _rup(9 * Cp, 32)
+        K = rup(9 * Cp, 32)
         rows = B * Ho * Wo
         col = (torch.zeros if K > 9 * Cp else torch.empty)(rows, K, device=dev, dtype=torch.float32)
         _call("srn_im2col_s2", x, col, B, H, W, Cp, K)
@@ -648,7 +640,7 @@ class ParamStore:
         offs, o = [], 0
         for n in sizes:  # 4-float alignment of every view (16-B loads in the kernels)
             offs.append(o)
-            o += _rup(n, 4)
+            o += rup(n, 4)
         self.device = device
         self.flat = torch.zeros(o, device=device, dtype=torch.float32)
         self.flat_grad = torch.zeros(o, device=device, dtype=torch.float32)
@@ -747,7 +739,7 @@ class Estimator:
                 first.append((w, self._wd[name], 1, n, c, 0, c, 0, n))
             elif w.dim() == 3:
                 n, c, k = w.shape
-                c_pad = _rup(c, 32) if name.startswith("down_blocks.0.0.") and c == cin0 else c
+                c_pad = rup(c, 32) if name.startswith("down_blocks.0.0.") and c == cin0 else c
                 self._wd[name] = z(c_pad, k * n)
                 if k == 1 and c_pad == c:  # pack_conv is a view
                     first.append((w, self._wd[name], 1, n, c, 0, c, 0, n))
@@ -829,13 +821,13 @@ class Estimator:
                 raise ValueError("Estimator.forward: `mask` must be a length (prefix) mask, as make_non_pad_mask builds it")
         h = torch.cat([x, mu], dim=1).transpose(1, 2)  # (B, L, 242) channels-last
         cin = h.shape[-1]
-        cp = _rup(cin, 32)
+        cp = rup(cin, 32)
         h = F.pad(h, (0, cp - cin)).contiguous()
         t = torch.as_tensor(t, device=x.device, dtype=torch.float32).reshape(-1)
         if t.numel() == 1:
             t = t.expand(B)
         s = sinusoidal_pos_emb(t, cin)
-        s = F.pad(s, (0, _rup(cin, 4) - cin))
+        s = F.pad(s, (0, rup(cin, 4) - cin))
         temb = self._lin(F.silu(self._lin(s, "time_mlp.linear_1", c_pad=s.shape[1])), "time_mlp.linear_2")
         spk = spks.to(torch.float32)
 
@@ -1168,7 +1160,7 @@ class GradSync:
         names = list(estimator.spans)
         for k in names:
             off, n = estimator.spans[k]
-            end = off + _rup(n, 4)
+            end = off + rup(n, 4)
             if end - lo >= per or k == names[-1]:
                 self.buckets.append((lo, total if k == names[-1] else end))
                 lo = end

@@ -44,8 +44,8 @@ import torch
 
 from . import _lib, ops, pitch
 from .features import _slaney_mel, _Stft
-from .models import _lru_get, _rup
 from .ops import ConvOp, GraphRunner
+from .plan import check_state, linear_op, lru_get, rup, wave_batch
 
 __all__ = ["TranscriptionModel", "FramewiseDecoder", "estimate_score", "reference_f0", "DEFAULT_CONFIG"]
 
@@ -154,7 +154,7 @@ class TranscriptionModel:
 
     def _pack_stack(self, s, pre, F, m, d):
         c0, c2 = m // 16, m // 8
-        p0, p2 = _rup(c0, 4), _rup(c2, 4)
+        p0, p2 = rup(c0, 4), rup(c2, 4)
         convs = []
         for (ci, bi), (co, cin, cop, cip) in zip(_CONVS, ((c0, 1, p0, 1), (c0, c0, p0, p0), (c2, c0, p2, p0))):
             bn = [s[f"{pre}cnn.{bi}.{k}"] for k in ("weight", "bias", "running_mean", "running_var")]
@@ -170,7 +170,7 @@ class TranscriptionModel:
                 wp = wp.reshape(cop, 9 * cip)
             convs.append((d(wp), d(bp)))
         K = c2 * (F // 4)
-        fw = torch.zeros(m, _rup(K, 4))
+        fw = torch.zeros(m, rup(K, 4))
         fw[:, :K] = s[f"{pre}fc.0.weight"]
         return {"convs": convs, "fc_w": d(fw), "fc_b": d(s[f"{pre}fc.0.bias"]), "F": F, "m": m, "c2": c2}
 
@@ -187,13 +187,7 @@ class TranscriptionModel:
     def load_state_dict(self, sd):
         s = {k: torch.as_tensor(v).detach().cpu() for k, v in sd.items()}
         want = self.state_shapes()
-        missing = [k for k in want if k not in s]
-        unexpected = sorted(k for k in s if k not in want and not self._ignored(k))
-        if missing or unexpected:
-            raise KeyError(f"TranscriptionModel.load_state_dict: missing {missing[:8]}, unexpected {unexpected[:8]}")
-        for k, shp in want.items():
-            if tuple(s[k].shape) != shp:
-                raise ValueError(f"TranscriptionModel.load_state_dict: {k} has shape {tuple(s[k].shape)}, expected {shp}")
+        check_state("TranscriptionModel.load_state_dict", s, want, ignored=[k for k in s if self._ignored(k)])
         c, lc = self.config, self.config["lang_model_config"]
         dev = self.device
         d = lambda t: t.to(dev, torch.float32).contiguous()
@@ -228,32 +222,14 @@ class TranscriptionModel:
         logits (B, T, 39).  Frames at or past an item's count are padding (unspecified values)."""
         if self.w is None:
             raise RuntimeError("TranscriptionModel: load_state_dict first")
-        if not isinstance(wave16k, torch.Tensor):
-            wave16k = torch.as_tensor(np.asarray(wave16k, dtype=np.float32))
-        a = wave16k.detach()
-        if a.dim() == 3:
-            if a.shape[1] != 1:
-                raise ValueError("TranscriptionModel: a 3-D wave must be (B, 1, n)")
-            a = a[:, 0]
-        if a.dim() == 1:
-            a = a.unsqueeze(0)
-        if a.dim() != 2:
-            raise ValueError("TranscriptionModel: wave16k must be (n,), (B, n) or (B, 1, n)")
-        if not a.is_cuda:
-            if self.device.type != "cuda":
-                raise RuntimeError("TranscriptionModel needs a CUDA (ROCm) device; there is no CPU fallback")
-            a = a.to(self.device)
-        a = a.to(torch.float32)
+        a, lens = wave_batch(wave16k, lengths, self.device, "TranscriptionModel", allow_channel_dim=True)
         B, n = a.shape
-        lens = [n] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-        if len(lens) != B or max(lens) > n or min(lens) < 1:
-            raise ValueError(f"TranscriptionModel: lengths {lens} do not fit a batch of {B} x {n} samples")
         pad = max(self.config["win_length"], self.config["lang_model_config"]["win_length"]) // 2
         if min(lens) <= pad:
             raise ValueError(f"TranscriptionModel: an utterance of {min(lens)} samples is too short for the reflect "
                              f"padding of {pad}")
         key = (str(a.device), B, n, tuple(lens))
-        plan = _lru_get(self._plans, key, 8, lambda: _Plan(self, a.device, B, n, lens))
+        plan = lru_get(self._plans, key, 8, lambda: _Plan(self, a.device, B, n, lens))
         plan.wave.copy_(a, non_blocking=True)
         plan.run()
         T = [self.frames(v) for v in lens]
@@ -278,7 +254,6 @@ class _Plan:
         self.lens = i32(tl)
         self.wave = f(B, n)
         self._lens_cache = {}
-        self._keep = []
         ol = []
         # ---- front-ends: one STFT per distinct (n_fft, hop), then mel power -> dB -> per-item top_db clamp
         samples = i32(lens)
@@ -298,13 +273,12 @@ class _Plan:
             ol.append(ops.CallOp("srn_mel_db", (st.spec, st.ld, st.nb, mel_t, self.lens, gmax, img, cc["n_mels"], B, T,
                                                 cc["n_mels"], AMIN, TOP_DB)))
             imgs[which] = img
-        self._keep += [samples, stfts, gmax, imgs]
         # ---- phoneme model: ConvStack -> BiLSTM -> Linear(39) (40 columns, the last one zero)
         x, _ = self._stack(ol, f, imgs["lang"], lc["n_mels"], lc["n_mels"], w["phon_stack"], 1)
         h = f(B, T, m.m_lang)
         self._bilstm(ol, f, x, w["phon_rnn"], h, 0, m.m_lang)
         self.phon = f(B, T, N_PHONEMES + 1)
-        ol.append(self._lin(h, m.m_lang, *w["phon_fc"], self.phon, N_PHONEMES + 1))
+        ol.append(linear_op(h, B * T, m.m_lang, *w["phon_fc"], self.phon, N_PHONEMES + 1, precision=_lib.PREC_FP32))
         # ---- lang and pitch branches into the two halves of the combined BiLSTM's input
         cat = f(B, T, 2 * m.m)
         x, _ = self._stack(ol, f, self.phon, N_PHONEMES + 1, N_PHONEMES, w["lang_stack"], 2)
@@ -314,8 +288,7 @@ class _Plan:
         comb = f(B, T, m.m)
         self._bilstm(ol, f, cat, w["comb_rnn"], comb, 0, m.m)
         self.logits = f(B, T, 4)
-        ol.append(self._lin(comb, m.m, *w["comb_fc"], self.logits, 4))
-        self._keep += [h, cat, comb]
+        ol.append(linear_op(comb, B * T, m.m, *w["comb_fc"], self.logits, 4, precision=_lib.PREC_FP32))
         self.ops = ol
         self.runner = GraphRunner(lambda: self.ops)
 
@@ -323,11 +296,6 @@ class _Plan:
         if k not in self._lens_cache:
             self._lens_cache[k] = (self.lens * k).contiguous()
         return self._lens_cache[k]
-
-    def _lin(self, inp, K, wt, b, out, N):
-        rows = self.B * self.T
-        return ConvOp(in0=inp, w=wt, out=out, n_batch=1, T_in=rows, T_out=rows, C_in=K, N=N, ld_in0=K, ldw=K, ld_out=N,
-                      bias=b, precision=_lib.PREC_FP32)
 
     def _conv3x3(self, inp, wb, out, F, cin, cout):
         """3x3 conv (padding 1) + folded BN + ReLU on a bordered channels-last image (B, T, F + 2, cin): the rows of an
@@ -348,25 +316,23 @@ class _Plan:
         a0, a1 = f(B, T, F + 2, p0), f(B, T, F + 2, p0)
         q1, a2 = f(B, T, F2 + 2, p0), f(B, T, F2 + 2, p2)
         K = sw["c2"] * F4
-        flat = f(B, T, _rup(K, 4))
+        flat = f(B, T, rup(K, 4))
         out = f(B, T, sw["m"])
         ol.append(ops.CallOp("srn_trans_conv0", (img, T * ld_img, ld_img, self.lens, w0, b0, a0, B, T, F, p0, dil)))
         ol.append(self._conv3x3(a0, c1, a1, F, p0, p0))
         ol.append(ops.CallOp("srn_trans_pool", (a1, self.lens, q1, B, T, F, p0, p0, 0, 0)))
         ol.append(self._conv3x3(q1, c2w, a2, F2, p0, p2))
-        ol.append(ops.CallOp("srn_trans_pool", (a2, self.lens, flat, B, T, F2, p2, sw["c2"], 1, _rup(K, 4))))
-        ol.append(self._lin(flat, _rup(K, 4), sw["fc_w"], sw["fc_b"], out, sw["m"]))
-        self._keep += [a0, a1, q1, a2, flat, out]
+        ol.append(ops.CallOp("srn_trans_pool", (a2, self.lens, flat, B, T, F2, p2, sw["c2"], 1, rup(K, 4))))
+        ol.append(linear_op(flat, B * T, rup(K, 4), sw["fc_w"], sw["fc_b"], out, sw["m"], precision=_lib.PREC_FP32))
         return out, sw["m"]
 
     def _bilstm(self, ol, f, x, lw, out, col0, ld_out):
         """BiLSTM(x) -> out[:, :, col0 : col0 + 2H] (row length ld_out)"""
         B, T, H, I = self.B, self.T, lw["H"], lw["I"]
         g = f(B, T, 8 * H)
-        ol.append(self._lin(x, I, lw["w_ih"], lw["b"], g, 8 * H))
+        ol.append(linear_op(x, B * T, I, lw["w_ih"], lw["b"], g, 8 * H, precision=_lib.PREC_FP32))
         ol.append(ops.CallOp("srn_bilstm_recur", (g, T * 8 * H, 8 * H, self.lens, lw["w_hh_t"], (out, col0), T * ld_out,
                                                   ld_out, B, T, H)))
-        self._keep.append(g)
 
     def run(self):
         self.runner()

@@ -11,6 +11,7 @@ Everything is computed channels-last by libserenade_hip.so: the transposed convo
 implicit-GEMM launch per output phase (2 taps each), every residual-stack conv has the LeakyReLU
 fused into its input gather and bias / residual / stage-mean fused into its epilogue.
 """
+import functools
 import logging
 import os
 import time
@@ -19,8 +20,9 @@ import torch
 import yaml
 
 from . import _shapes, ops
-from .models import _Packed, _dev_f32, _fold_wn, _lru_get, _require_cuda
-from .ops import ACT_LEAKY, POST_DIV, POST_LEAKY, RES_ADD, ConvOp
+from .models import _Packed, _fold_wn
+from .ops import ACT_LEAKY, POST_DIV, POST_LEAKY, RES_ADD
+from .plan import conv_op, dev_f32, lru_get, require_cuda as _require_cuda
 
 __all__ = ["HiFiGANGenerator", "Vocoder", "load_vocoder", "hifigan_state_shapes"]
 
@@ -95,7 +97,7 @@ class HiFiGANGenerator(_Packed):
     def packed(self):
         if self._packed is None:
             dev = self._device()
-            sd = {k: _dev_f32(v, dev) for k, v in self._own_state().items() if k not in ("mean", "scale")}
+            sd = {k: dev_f32(v, dev) for k, v in self._own_state().items() if k not in ("mean", "scale")}
             P = dict(in_w=ops.pack_conv_weight(_fold_wn(sd, "input_conv")), in_b=sd["input_conv.bias"], ups=[],
                      blocks=[])
             for i, s in enumerate(self.upsample_scales):
@@ -122,7 +124,7 @@ class HiFiGANGenerator(_Packed):
 
     def plan(self, B, T):
         key = (B, T, ops.DEFAULT_PRECISION)
-        return _lru_get(self._plans, key, 4, lambda: HiFiGANPlan(self, B, T))
+        return lru_get(self._plans, key, 4, lambda: HiFiGANPlan(self, B, T))
 
     @torch.no_grad()
     def forward(self, c):
@@ -187,11 +189,7 @@ class HiFiGANPlan:
         slope = gen.slope
         ol = []
 
-        def conv(inp, cin, T_in, w, b, out, cout, T_out, taps, **kw):
-            return ConvOp(in0=inp, w=w, out=out, n_batch=B, T_in=T_in, T_out=T_out, C_in=cin, N=cout,
-                          in0_bs=T_in * cin, ld_in0=cin, ldw=w.shape[1], out_bs=kw.pop("out_bs", T_out * cout),
-                          ld_out=cout, bias=b, taps=taps, **kw)
-
+        conv = functools.partial(conv_op, B)
         ol.append(conv(self.c_in, gen.in_channels, T, P["in_w"], P["in_b"], h, C0, T, ops.conv_taps(gen.kernel_size)))
         cur, ccur, tcur = h, C0, T
         nb = gen.num_blocks
@@ -237,7 +235,6 @@ class HiFiGANPlan:
         ol.append(ops.out_conv_tanh_op(cur, P["out_w"], P["out_b"], self.wave, B, tcur, ccur, gen.kernel_size, 0.01))
         self.ops = ol
         self._runner = ops.GraphRunner(lambda: self.ops)
-        self._keep = (h, u, p0, p1, xt, acc)
 
     def run(self):
         self._runner()

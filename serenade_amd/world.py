@@ -31,6 +31,7 @@ import torch
 from . import _lib
 from ._lib import SrnExcitationParams, SrnWorldParams, check
 from .ops import _stream
+from .plan import require_cuda as _require_cuda
 
 __all__ = ["ALPHA", "harvest_frame_count", "harvest_time_axis", "cheaptrick", "cheaptrick_fft_size",
            "d4c_band_aperiodicity", "sp2mc", "match_length", "convert_continuos_f0", "Analyzer"]
@@ -124,11 +125,6 @@ def _sp2mc_matrix(dev, n_bins, order, alpha, from_cepstrum):
 
 
 # ------------------------------------------------------------------------------------------------ argument plumbing
-def _require_cuda(t, what):
-    if not (torch.is_tensor(t) and t.is_cuda):
-        raise RuntimeError(f"{what}: expected a CUDA tensor (this module has no CPU path)")
-
-
 def _as_f64(v, dev):
     if torch.is_tensor(v):
         return v.to(device=dev, dtype=_F64).contiguous()

@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from oracle import serenade_oracle as O
-from serenade_amd import models, vocoder
+from serenade_amd import models, plan, vocoder
 from serenade_amd.utils.synth import HIFIGAN_PARAMS, SERENADE_PARAMS, fill_state_dict, synth_inputs
 from tests import _emulator
 from tests._weights import hifigan_weights, serenade_weights, sub
@@ -48,10 +48,10 @@ def test_attention_chunking_is_invisible(model, golden, monkeypatch, pairs):
     item's 4 heads) must give the decoder output of the unchunked plan (padded batch of 2, odd L)"""
     g = golden("decoder_L65")
     L = 65
-    monkeypatch.setattr(models, "S_BUDGET", pairs * L * 96 * 4)  # rup(65, 32) = 96
+    monkeypatch.setattr(plan, "S_BUDGET", pairs * L * 96 * 4)  # rup(65, 32) = 96
     est = model.cfm_decoder.estimator
     est._plans.clear()
-    assert len(models.attention_chunks(2, 4, L * 96 * 4, pairs * L * 96 * 4)) == {1: 8, 3: 4, 4: 2}[pairs]
+    assert len(plan.attention_chunks(2, 4, L * 96 * 4, pairs * L * 96 * 4)) == {1: 8, 3: 4, 4: 2}[pairs]
     mask = O.make_non_pad_mask(g["lens"].tolist()).unsqueeze(1)
     with _emulator.installed():
         out = est(T(g["x"]), mask, T(g["mu"]), T(g["t"]), T(g["spk"]))

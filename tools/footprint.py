@@ -29,10 +29,9 @@ def main():
         voc.decode_batch(mel if mel.dim() == 3 else mel.unsqueeze(0))
         torch.cuda.synchronize()
         pl = model.cfm_decoder.estimator.plan(B, T + 256, 10, euler=True)
-        S = [t for t in pl._keep if isinstance(t, torch.Tensor) and t.dim() == 1]
         print(f"B={B} T={T}: weights {base / 2**30:.2f} GiB, total allocated {torch.cuda.memory_allocated() / 2**30:.2f} "
               f"GiB, peak {torch.cuda.max_memory_allocated() / 2**30:.2f} GiB; attention score buffer "
-              f"{max((t.numel() * 4 for t in S), default=0) / 2**20:.0f} MiB "
+              f"{pl.S.numel() * 4 / 2**20:.0f} MiB "
               f"(unchunked it would be {B * 4 * (T + 256) * ((T + 256 + 31) // 32 * 32) * 4 / 2**30:.2f} GiB)", flush=True)
         del model, voc, pl, mel, g, d
 
