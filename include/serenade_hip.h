@@ -188,7 +188,8 @@ int srn_layernorm(const float* x, const float* gamma, const float* beta, float* 
 /*
  * Row softmax of attention scores with a key-padding mask (F.scaled_dot_product_attention semantics at
  * transformer.py:292-301): s (Z, L, ld) in place; keys k >= lens[z / n_head] get probability 0;
- * columns [L, ld) are written as 0.
+ * columns [L, ld) are written as 0 whatever they held (the callers never zero the score buffer).  lens[b] >= 1: a row
+ * without a valid key has no softmax.  ld <= 9216.
  */
 int srn_softmax_rows(float* s, const int32_t* lens, int Z, int n_head, int L, int ld, void* stream);
 
@@ -492,7 +493,11 @@ int64_t srn_tn_gemm_workspace_bytes(const SrnTnGemmParams* p);
  * SURVEY 8 f4).  Channels-last rows throughout.
  */
 /* BatchNorm2d(training) + ReLU over `rows` x C: stats (2, C) = (batch mean, 1 / sqrt(biased var + eps)) kept for the
- * backward; running statistics updated like nn.BatchNorm2d (momentum, unbiased variance) when given.
+ * backward; running statistics updated like nn.BatchNorm2d (momentum, unbiased variance) when given.  rows == 1 (which
+ * nn.BatchNorm2d refuses in training mode): the variance is 0, and so is the variance the running statistics take in.
+ * The variance is formed from fp32 sums of x - x[0] (row 0 of each column as pivot), so a constant column gives exactly
+ * 0 and a nearly constant one keeps its digits; it assumes row 0 is an ordinary sample of its column (a conv output):
+ * a pivot many standard deviations from the column mean costs digits of mean and variance instead.
  * partial: srn_bn_chunks(rows) * 2 * C floats of scratch.  C % 4 == 0. */
 int srn_bn_chunks(int64_t rows);
 int srn_bn_relu_fwd(const float* x, const float* gamma, const float* beta, float* run_mean, float* run_var,

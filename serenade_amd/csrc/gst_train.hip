@@ -23,7 +23,10 @@ __host__ __device__ inline int64_t bn_rows_per_chunk(int64_t R) { return R <= 25
 // 32 .. 128 -- the spare threads take further rows of the chunk (256 / (C / 4) row lanes), joined in lane order through
 // LDS; bn_finish_kernel adds the chunks)
 
-// mode 0: partial[chunk][0][c] = sum x, [1][c] = sum x^2
+// mode 0: partial[chunk][0][c] = sum (x - p), [1][c] = sum (x - p)^2 with the pivot p[c] = x[0][c] (the column's first
+//         row): the variance is then formed from differences of the data, not as E[x^2] - mean^2 of the raw values,
+//         whose fp32 squares are rounded at 2^-24 x^2 -- more than the variance itself once it falls below 1e-7 of the
+//         squared mean, and never zero for a single row, where it has to be
 // mode 1: g = dy * (y > 0): [0][c] = sum g, [1][c] = sum g * xhat,  xhat = (x - mean) * rstd
 __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                          const float* __restrict__ dy, const float* __restrict__ stats,
@@ -40,8 +43,10 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
   float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
   if (live) {
     if (mode == 0) {
+      const float4 p = *reinterpret_cast<const float4*>(x + c);
       for (int64_t r = r0 + rl; r < r1; r += lanes) {
-        const float4 v = *reinterpret_cast<const float4*>(x + r * C + c);
+        float4 v = *reinterpret_cast<const float4*>(x + r * C + c);
+        v.x -= p.x, v.y -= p.y, v.z -= p.z, v.w -= p.w;
         s0.x += v.x, s0.y += v.y, s0.z += v.z, s0.w += v.w;
         s1.x += v.x * v.x, s1.y += v.y * v.y, s1.z += v.z * v.z, s1.w += v.w * v.w;
       }
@@ -79,9 +84,11 @@ inline unsigned bn_channel_blocks(int C) {
 }
 
 // sums the chunks in a fixed order (four interleaved runs per channel, combined 0..3).  mode 0: stats = (mean, rstd) with
-// the biased batch variance, running statistics updated like nn.BatchNorm2d (momentum, unbiased variance).
+// the biased batch variance (from the pivot-shifted sums: pivot = row 0 of x), running statistics updated like
+// nn.BatchNorm2d (momentum, unbiased variance).
 // mode 1: out = (sum g, sum g xhat) = (dbeta, dgamma).  64 channels x 4 runs per workgroup.
-__global__ __launch_bounds__(256) void bn_finish_kernel(const float* __restrict__ partial, float* __restrict__ out,
+__global__ __launch_bounds__(256) void bn_finish_kernel(const float* __restrict__ partial,
+                                                        const float* __restrict__ pivot, float* __restrict__ out,
                                                         float* __restrict__ run_mean, float* __restrict__ run_var,
                                                         int n_chunk, int64_t R, int C, float eps, float momentum,
                                                         int mode) {
@@ -101,9 +108,9 @@ __global__ __launch_bounds__(256) void bn_finish_kernel(const float* __restrict_
   s0 = (red[0][0][lc] + red[0][1][lc]) + (red[0][2][lc] + red[0][3][lc]);
   s1 = (red[1][0][lc] + red[1][1][lc]) + (red[1][2][lc] + red[1][3][lc]);
   if (mode == 0) {
-    const double mean_d = (double)s0 / (double)R;
-    const float mean = (float)mean_d;
-    const float var = (float)fmax((double)s1 / (double)R - mean_d * mean_d, 0.0);
+    const double shift_d = (double)s0 / (double)R;  // mean of x - pivot
+    const float mean = (float)((double)pivot[c] + shift_d);
+    const float var = (float)fmax((double)s1 / (double)R - shift_d * shift_d, 0.0);
     out[c] = mean;
     out[C + c] = 1.0f / sqrtf(var + eps);
     if (run_mean) {
@@ -380,8 +387,8 @@ extern "C" int srn_bn_relu_fwd(const float* x, const float* gamma, const float* 
   const unsigned cb = bn_channel_blocks(C);
   hipLaunchKernelGGL(bn_partial_kernel, dim3(cb, chunks), dim3(256), 0, st, x, (const float*)nullptr,
                      (const float*)nullptr, (const float*)nullptr, partial, rows, C, 0);
-  hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)((C + 63) / 64)), dim3(256), 0, st, (const float*)partial, stats,
-                     run_mean, run_var, chunks, rows, C, eps, momentum, 0);
+  hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)((C + 63) / 64)), dim3(256), 0, st, (const float*)partial, x,
+                     stats, run_mean, run_var, chunks, rows, C, eps, momentum, 0);
   const int64_t n4 = rows * C / 4;
   const unsigned blocks = (unsigned)((n4 + 255) / 256 > 2048 ? 2048 : (n4 + 255) / 256);
   hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks), dim3(256), 0, st, x, (const float*)nullptr, (const float*)nullptr,
@@ -399,8 +406,8 @@ extern "C" int srn_bn_relu_bwd(const float* x, const float* y, const float* dy, 
   hipStream_t st = (hipStream_t)stream;
   const unsigned cb = bn_channel_blocks(C);
   hipLaunchKernelGGL(bn_partial_kernel, dim3(cb, chunks), dim3(256), 0, st, x, y, dy, stats, partial, rows, C, 1);
-  hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)((C + 63) / 64)), dim3(256), 0, st, (const float*)partial, sums,
-                     (float*)nullptr, (float*)nullptr, chunks, rows, C, 0.f, 0.f, 1);
+  hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)((C + 63) / 64)), dim3(256), 0, st, (const float*)partial,
+                     (const float*)nullptr, sums, (float*)nullptr, (float*)nullptr, chunks, rows, C, 0.f, 0.f, 1);
   const int64_t n4 = rows * C / 4;
   const unsigned blocks = (unsigned)((n4 + 255) / 256 > 2048 ? 2048 : (n4 + 255) / 256);
   hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks), dim3(256), 0, st, x, y, dy, stats, (const float*)sums, gamma,

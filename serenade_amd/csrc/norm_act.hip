@@ -599,7 +599,7 @@ extern "C" int srn_softmax_rows(float* s, const int32_t* lens, int Z, int n_head
   else if (nv <= 20) hipLaunchKernelGGL(softmax_rows_kernel<20>, dim3(blocks), dim3(256), 0, st, s, lens, rows, n_head, L, ld);
   else if (nv <= 36) hipLaunchKernelGGL(softmax_rows_kernel<36>, dim3(blocks), dim3(256), 0, st, s, lens, rows, n_head, L, ld);
   else {
-    srn_set_error("softmax_rows: L=%d too long (max 9216)", L);
+    srn_set_error("softmax_rows: ld=%d too long (max 9216)", ld);
     return -1;
   }
   SRN_CHECK_LAUNCH();

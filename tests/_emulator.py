@@ -150,6 +150,16 @@ def _group_stats(partials, b, T, C, groups, eps, n_rows=None):
     return mean.float(), (1.0 / torch.sqrt(var + eps)).float()
 
 
+def _c_float(x):
+    """a Python float as it arrives behind the C ABI's `float` parameters: 1 - beta2 is formed from the ROUNDED beta2
+    (1 - float(0.999) is 1.3e-5 below 0.001)"""
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+def _sumsq_blocks(n):
+    return max(1, min(1024, ((n + 7) // 8 + 255) // 256))  # srn_sumsq_blocks
+
+
 def emul_call(name, a):
     if name == "srn_gn_mish_apply":
         x, part, gamma, beta, tb, tb_bs, lens, y, B, T, C, groups, eps, valid = a
@@ -476,16 +486,17 @@ def emul_call(name, a):
         _v(dhg, rows * 2 * inner).reshape(rows, 2 * inner)[:] = hv.grad
     elif name == "srn_dot":
         x, y, n, part = a
-        pv = _v(part)
+        pv = _v(part)[:_sumsq_blocks(n)]  # the entries past srn_sumsq_blocks(n) are the caller's
         pv.zero_()
         pv[0] = (_v(x, n).double() * (1.0 if y is None else _v(y, n).double())).sum()
     elif name == "srn_sumsq":
         g, n, part = a
-        pv = _v(part)
+        pv = _v(part)[:_sumsq_blocks(n)]
         pv.zero_()
         pv[0] = (_v(g, n).double() ** 2).sum()
     elif name == "srn_adamw_dyn":
         pp, g, m, v, n, b1, b2, eps, wd, dyn = a
+        b1, b2, eps, wd = (_c_float(x) for x in (b1, b2, eps, wd))
         lr, bc1, bc2, gscale = (float(x) for x in _v(dyn, 4))
         pv, gv, mv, vv = (_v(t, n) for t in (pp, g, m, v))
         gi = gv * gscale
@@ -495,6 +506,7 @@ def emul_call(name, a):
         pv.addcdiv_(mv / bc1, (vv / bc2).sqrt() + eps, value=-lr)
     elif name == "srn_adamw":
         pp, g, m, v, n, lr, b1, b2, eps, wd, step, gscale = a
+        lr, b1, b2, eps, wd, gscale = (_c_float(x) for x in (lr, b1, b2, eps, wd, gscale))
         pv, gv, mv, vv = (_v(t, n) for t in (pp, g, m, v))
         gi = gv * gscale
         pv.mul_(1 - lr * wd)

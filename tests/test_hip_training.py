@@ -1,6 +1,9 @@
 """SURVEY 8 f4 on the GPU: the estimator's training step (serenade_amd/training.py over libserenade_hip.so).
 
-  * every backward kernel of csrc/train.hip against torch autograd of the op it differentiates;
+  * the backward ops of training.py built on csrc/train.hip (conv, GroupNorm + Mish, row LayerNorm, attention core,
+    GEGLU, weight norm) against torch autograd of the op they differentiate, one shape each; the kernels of
+    csrc/gst_train.hip are reached here only through the whole-model gradient test.  The per-kernel sweeps of both
+    files (every C-ABI entry, edge shapes, float64 references, guard bands) are tests/test_hip_rowops.py;
   * loss + gradients of all 192 estimator parameters, d mu, d spks against the REFERENCE's own
     CFM.compute_loss + backward() (tests/golden/train_grads_L45.npz) and, at a larger ragged batch, against autograd
     through the CPU oracle;
