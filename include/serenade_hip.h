@@ -632,6 +632,73 @@ int srn_pyin_viterbi(const double* obs, const double* voiced_prob, const int32_t
                      uint16_t* ptr_ws, int32_t* states, double* f0, uint8_t* voiced_flag, int B, int T, int n_bins,
                      int width, void* stream);
 
+/*
+ * WORLD Harvest F0 estimation (Morise 2017, harvest.cpp) as pyworld.harvest runs it on every utterance of
+ * preprocessing (serenade/bin/preprocess.py:485-493: pyworld.harvest(audio, fs, f0_floor, f0_ceil, frame_period));
+ * serenade_amd/harvest.py drives the five entry points in this order.  fp64; tests/_harvest_ref.py is the
+ * restatement every one of them is held to.  Everything takes per-item lengths and frame counts: every item of a
+ * padded batch gets what its own B = 1 call gets and samples past an item's length are never read.  The body always
+ * works on 1 ms frames (frames[b] = int(1000 n / fs) + 1 of them, at most F1).  Limits: a channel's band-pass has
+ * at most SRN_HARVEST_MAX_TAPS taps (2 matlab_round(2 actual_fs / (0.9 f0_floor 2^(1/40))) + 1), the refinement's
+ * window 2 int(1.5 actual_fs / f0_floor + 1) + 1 at most SRN_HARVEST_MAX_WINDOW samples, at most
+ * SRN_HARVEST_MAX_CAND candidates per frame (7 matlab_round(n_ch / 10)), decimation ratio <= SRN_HARVEST_MAX_RATIO.
+ */
+#define SRN_HARVEST_MAX_TAPS 1024
+#define SRN_HARVEST_MAX_WINDOW 1536
+#define SRN_HARVEST_MAX_CAND 256
+#define SRN_HARVEST_MAX_RATIO 12
+#define SRN_HARVEST_SMOOTH_PAD 300
+/* preprocess.py:485-493 -> Harvest's GetWaveformAndSpectrum + decimate, one wave per item.  x (B, N) float32
+ * (x_is_f64 0) or float64 (1) at row stride x_bs, lens[b] <= N samples.  ratio > 1: the item extended by lag
+ * (a multiple of ratio, >= 10) copies of each edge sample, MATLAB-style zero-phase decimate (9 reflected samples, the
+ * order-3 filter coef = b[0..3], a[0..3] in direct form II from zero state, forwards then backwards), every ratio-th
+ * sample, the first lag / ratio dropped; ratio 1: a copy.  Then the mean over the item's ceil(lens[b] / ratio)
+ * samples is removed.  ws: B x ws_stride doubles of scratch, ws_stride >= N + 2 lag + 18 (unused for ratio 1).
+ * y (B, y_bs), y_bs >= ceil(N / ratio). */
+int srn_harvest_decimate(const void* x, int x_is_f64, int64_t x_bs, const int32_t* lens, const double* coef, double* ws,
+                         int64_t ws_stride, double* y, int64_t y_bs, int B, int N, int ratio, int lag, void* stream);
+/* preprocess.py:485-493 -> Harvest's GetRawF0Candidates (GetFilteredSignal, ZeroCrossingEngine x 4,
+ * GetF0CandidateContour), one workgroup per (channel, item) for the channels ch0 .. ch0 + n_launch - 1 of n_ch.
+ * y (B, y_bs): item b has ylens[b] <= max_ylen samples at fs (the decimated rate) and frames[b] 1 ms frames.  Channel
+ * c: taps[tap_off[c] .. + 2 half_len[c]] (Nuttall window x cosine at boundary[c], built on the host), max_half_len
+ * the largest half length.  The band-pass is the linear convolution taken at index bias half_len + 1, zeros outside
+ * the item.  events: B x n_launch x 4 x ev_cap doubles of scratch, ev_cap >= max_ylen / 2 (an edge needs two
+ * samples, so no kind of event can have more).  raw (B, n_ch, F1): the channel's candidate at every frame, 0 where
+ * any kind of event has fewer than 3 intervals, where the average of the four interpolated contours is outside
+ * [0.9, 1.1] boundary[c] or [f0_floor, f0_ceil], and on frames past frames[b]. */
+int srn_harvest_channels(const double* y, int64_t y_bs, const int32_t* ylens, const int32_t* frames, const double* taps,
+                         const int32_t* tap_off, const int32_t* half_len, const double* boundary, int max_half_len,
+                         double* events, int64_t ev_cap, double* raw, int B, int ch0, int n_launch, int n_ch, int F1,
+                         int max_ylen, double fs, double f0_floor, double f0_ceil, void* stream);
+/* preprocess.py:485-493 -> Harvest's DetectOfficialF0Candidates + OverlapF0Candidates, one thread per (item, frame).
+ * official (B, F1, n_base): the means of raw over every run of >= 10 channels with a candidate (first and last channel
+ * ignored), in channel order, zero-filled.  cand (B, F1, 7 n_base): block 0 the frame's own, blocks 1-3 those of the
+ * frames 1-3 before, blocks 4-6 those of the frames 1-3 after; a missing neighbour gives 0. */
+int srn_harvest_candidates(const double* raw, const int32_t* frames, double* official, double* cand, int B, int n_ch,
+                           int F1, int n_base, void* stream);
+/* preprocess.py:485-493 -> Harvest's RefineF0Candidates (GetRefinedF0), one wave per (item, frame) over the frame's
+ * non-zero candidates: Blackman-type window of 2 int(1.5 fs / f0 + 1) + 1 samples centred on the frame's time and its
+ * central-difference derivative, sample indices clamped into the item, a direct DFT at the bins of the first
+ * min(int(fs / 2 / f0), 6) harmonics, the instantaneous frequency of each, refined (B, F1, n_cand) = their
+ * amplitude-weighted F0 and score = 1 / (1e-12 + mean relative deviation); both 0 where refined is outside
+ * [f0_floor, f0_ceil] or score < 2.5. */
+int srn_harvest_refine(const double* y, int64_t y_bs, const int32_t* ylens, const int32_t* frames, const double* cand,
+                       double* refined, double* score, int B, int F1, int n_cand, double fs, double f0_floor,
+                       double f0_ceil, void* stream);
+/* preprocess.py:485-493 -> Harvest's RemoveUnreliableCandidates (one thread per candidate, into cand2 / score2
+ * (B, F1, n_cand)), then one workgroup per item: SearchF0Base, FixStep1-4 (Extend runs one wave per voiced section),
+ * SmoothF0Contour (one lane per section, smooth_coef = b[0..2], a[0..2], SRN_HARVEST_SMOOTH_PAD frames of padding) and
+ * the pick f0_out[b][i] = smoothed[min(frames[b] - 1, matlab_round(i frame_period))] for i < out_frames[b], 0 up to
+ * F_out.  fbuf (B, 6, F1): [0] the best candidates, [3] the contour before smoothing, [4] the smoothed 1 ms contour.
+ * pool: B x pool_stride doubles, sections: B x 7 x sec_cap int32 of scratch; status[b] != 0 reports that item b had
+ * more voiced sections than sec_cap or pool_stride hold (sec_cap >= F1 / min(voice_range_minimum + 2, 10) + 4 and
+ * pool_stride >= F1 + 600 sec_cap always suffice). */
+int srn_harvest_contour(const double* refined, const double* score, const int32_t* frames, const int32_t* out_frames,
+                        const double* smooth_coef, double* cand2, double* score2, double* fbuf, double* pool,
+                        int64_t pool_stride, int32_t* sections, int sec_cap, int32_t* status, double* f0_out,
+                        int64_t out_stride, int B, int F1, int n_cand, int F_out, int voice_range_minimum,
+                        double frame_period, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,12 @@ _SIGS = {
     "srn_bilstm_recur": (c_int, [_P, c_int64, c_int, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, _P]),
     "srn_pyin_observe": (c_int, [_P, c_int64] + [_P] * 9 + [c_int] * 10 + [c_double] * 3 + [c_int, _P]),
     "srn_pyin_viterbi": (c_int, [_P] * 6 + [c_double] * 2 + [c_int] + [_P] * 4 + [c_int] * 4 + [_P]),
+    "srn_harvest_decimate": (c_int, [_P, c_int, c_int64, _P, _P, _P, c_int64, _P, c_int64] + [c_int] * 4 + [_P]),
+    "srn_harvest_channels": (c_int, [_P, c_int64] + [_P] * 6 + [c_int, _P, c_int64, _P] + [c_int] * 6
+                             + [c_double] * 3 + [_P]),
+    "srn_harvest_candidates": (c_int, [_P] * 4 + [c_int] * 4 + [_P]),
+    "srn_harvest_refine": (c_int, [_P, c_int64] + [_P] * 5 + [c_int] * 3 + [c_double] * 3 + [_P]),
+    "srn_harvest_contour": (c_int, [_P] * 9 + [c_int64, _P, c_int, _P, _P, c_int64] + [c_int] * 5 + [c_double, _P]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -34,7 +34,8 @@ from .ops import _stream
 from .plan import require_cuda as _require_cuda
 
 __all__ = ["ALPHA", "harvest_frame_count", "harvest_time_axis", "cheaptrick", "cheaptrick_fft_size",
-           "d4c_band_aperiodicity", "sp2mc", "match_length", "convert_continuos_f0", "Analyzer"]
+           "d4c_band_aperiodicity", "sp2mc", "match_length", "convert_continuos_f0", "Analyzer", "harvest",
+           "extract_f0"]
 
 # all-pass constants of the mel-cepstral warp per sampling rate (ssc_postprocessing.py:39-48; public SPTK values)
 ALPHA = {8000: 0.312, 12000: 0.369, 16000: 0.410, 22050: 0.455, 24000: 0.466, 32000: 0.504, 44100: 0.544,
@@ -381,3 +382,7 @@ class Analyzer:
         feats = self.features(wave, lengths, f0_list)
         in_signal, dfs = self.excitation(feats, noise, generator)
         return in_signal, feats["c"], dfs, feats
+
+
+# preprocessing's Harvest (preprocess.py:485-493) lives in harvest.py; stage 9 above keeps only its frame count
+from .harvest import extract_f0, harvest  # noqa: E402,F401
