@@ -35,8 +35,8 @@ import numpy as np
 import scipy.signal
 import torch
 
-from . import _lib
-from .plan import lru_get
+from . import ops
+from .plan import dev_f64, dev_i32, item_lengths, lru_get
 
 __all__ = ["harvest", "extract_f0", "harvest_geometry", "harvest_frames", "harvest_pick", "decimation_table",
            "smoothing_table", "channel_taps"]
@@ -79,7 +79,8 @@ def harvest_geometry(fs, f0_floor=71.0, f0_ceil=800.0):
 
 
 def harvest_frames(x_length, fs, frame_period=5.0):
-    """frames pyworld.harvest returns (WORLD GetSamplesForHarvest); the body itself always runs at frame_period 1"""
+    """frames pyworld.harvest returns (WORLD GetSamplesForHarvest); the body itself always runs at frame_period 1.
+    Stage 9 (world.py, as `harvest_frame_count`) keeps nothing else of Harvest."""
     return int(1000.0 * x_length / fs / frame_period) + 1
 
 
@@ -100,14 +101,17 @@ def smoothing_table():
     return scipy.signal.butter(*SMOOTH_FILTER)
 
 
+def nuttall_window(n):
+    """WORLD's NuttallWindow of n samples (float64): the band-passes here, D4C's band window in world.py"""
+    t = np.arange(n) / (n - 1.0)
+    a = NUTTALL
+    return a[0] - a[1] * np.cos(2.0 * np.pi * t) + a[2] * np.cos(4.0 * np.pi * t) - a[3] * np.cos(6.0 * np.pi * t)
+
+
 def channel_taps(boundary_f0, actual_fs):
     """a channel's band-pass: Nuttall window of 2 hl + 1 samples x cosine at boundary_f0, hl = round(2 fs / f0)"""
     hl = matlab_round(actual_fs / boundary_f0 * FILTER_PERIODS)
-    n = 2 * hl + 1
-    t = np.arange(n) / (n - 1.0)
-    a = NUTTALL
-    win = a[0] - a[1] * np.cos(2.0 * np.pi * t) + a[2] * np.cos(4.0 * np.pi * t) - a[3] * np.cos(6.0 * np.pi * t)
-    return win * np.cos(2.0 * np.pi * boundary_f0 * np.arange(-hl, hl + 1) / actual_fs)
+    return nuttall_window(2 * hl + 1) * np.cos(2.0 * np.pi * boundary_f0 * np.arange(-hl, hl + 1) / actual_fs)
 
 
 def _check(fs, f0_floor, f0_ceil, frame_period):
@@ -142,9 +146,15 @@ def _sizes(g, lengths, fs):
     return F1, ylen, sec_cap, pool, per_item
 
 
+def _require_cuda(x):
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in (torch.float32, torch.float64)):
+        raise RuntimeError("harvest: x must be a float32 or float64 CUDA (ROCm) tensor; there is no CPU path")
+
+
 class _HarvestPlan:
-    """tables and buffers of one (device, B, N, lengths, parameters) call; the five steps are methods so that the tests
-    and tools/harvestbench.py can run and time them one by one (each reads the buffers the previous one wrote)"""
+    """tables, buffers and prebuilt ops of one (device, B, N, lengths, parameters) call; the five steps are methods so
+    that the tests and tools/harvestbench.py can run and time them one by one (each reads the buffers the previous one
+    wrote).  Only the decimation reads the caller's x, so only its op is built per call."""
 
     def __init__(self, dev, B, N, lengths, key):
         fs, f0_floor, f0_ceil, frame_period, is_f64 = key
@@ -157,14 +167,13 @@ class _HarvestPlan:
         self.ylens = [-(-n // g["ratio"]) for n in lengths]
         self.F1, self.ylen, self.sec_cap, self.pool_stride, _ = _sizes(g, lengths, fs)
         self.F = max(self.out_frames)
-        i32 = lambda a: torch.tensor(a, dtype=torch.int32, device=dev)
-        f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+        i32, f64 = (lambda a: dev_i32(a, dev)), (lambda a: dev_f64(a, dev))
         z64 = lambda *s: torch.zeros(*s, dtype=torch.float64, device=dev)
-        self.d_lens, self.d_ylens = i32(list(lengths)), i32(self.ylens)
+        self.d_lens, self.d_ylens = i32(lengths), i32(self.ylens)
         self.d_frames, self.d_out_frames = i32(self.frames), i32(self.out_frames)
         taps = [channel_taps(b, g["actual_fs"]) for b in g["boundary"]]
         self.taps = f64(np.concatenate(taps))
-        self.tap_off = i32(np.concatenate([[0], np.cumsum([len(t) for t in taps])[:-1]]).tolist())
+        self.tap_off = i32(np.concatenate([[0], np.cumsum([len(t) for t in taps])[:-1]]))
         self.half_len, self.boundary = i32(g["half_len"]), f64(g["boundary"])
         self.dec_coef = f64(np.concatenate(decimation_table(g["ratio"])))
         self.smooth_coef = f64(np.concatenate(smoothing_table()))
@@ -185,46 +194,42 @@ class _HarvestPlan:
         self.status = torch.zeros(B, dtype=torch.int32, device=dev)
         self.f0 = z64(B, self.F)
 
+        n_ch, fs_a, call = g["n_ch"], g["actual_fs"], ops.CallOp
+        self._channels = [call("srn_harvest_channels", (
+            self.y, self.y.stride(0), self.d_ylens, self.d_frames, self.taps, self.tap_off, self.half_len,
+            self.boundary, max(g["half_len"]), self.events, self.ev_cap, self.raw, B, ch0,
+            min(self.ch_chunk, n_ch - ch0), n_ch, F1, self.ylen, fs_a, self.f0_floor, self.f0_ceil))
+            for ch0 in range(0, n_ch, self.ch_chunk)]
+        self._candidates = call("srn_harvest_candidates", (
+            self.raw, self.d_frames, self.official, self.cand, B, n_ch, F1, g["n_base"]))
+        self._refine = call("srn_harvest_refine", (
+            self.y, self.y.stride(0), self.d_ylens, self.d_frames, self.cand, self.refined, self.score, B, F1, C, fs_a,
+            self.f0_floor, self.f0_ceil))
+        self._contour = call("srn_harvest_contour", (
+            self.refined, self.score, self.d_frames, self.d_out_frames, self.smooth_coef, self.cand2, self.score2,
+            self.fbuf, self.pool, self.pool_stride, self.sections, self.sec_cap, self.status, self.f0,
+            self.f0.stride(0), B, F1, C, self.F, g["voice_range_minimum"], self.frame_period))
+
     def decimate(self, x, stream):
         g = self.g
-        _lib.check(_lib.lib().srn_harvest_decimate(
-            x.data_ptr(), self.is_f64, x.stride(0), self.d_lens.data_ptr(), self.dec_coef.data_ptr(),
-            self.ws.data_ptr() if self.ws is not None else None, self.ws_stride, self.y.data_ptr(), self.y.stride(0),
-            self.B, self.N, g["ratio"], g["lag"], stream), "srn_harvest_decimate")
+        ops.CallOp("srn_harvest_decimate", (
+            x, self.is_f64, x.stride(0), self.d_lens, self.dec_coef, self.ws, self.ws_stride, self.y, self.y.stride(0),
+            self.B, self.N, g["ratio"], g["lag"]))(stream)
 
     def channels(self, stream):
-        g, lib = self.g, _lib.lib()
-        for ch0 in range(0, g["n_ch"], self.ch_chunk):
-            _lib.check(lib.srn_harvest_channels(
-                self.y.data_ptr(), self.y.stride(0), self.d_ylens.data_ptr(), self.d_frames.data_ptr(),
-                self.taps.data_ptr(), self.tap_off.data_ptr(), self.half_len.data_ptr(), self.boundary.data_ptr(),
-                max(g["half_len"]), self.events.data_ptr(), self.ev_cap, self.raw.data_ptr(), self.B, ch0,
-                min(self.ch_chunk, g["n_ch"] - ch0), g["n_ch"], self.F1, self.ylen, g["actual_fs"], self.f0_floor,
-                self.f0_ceil, stream), "srn_harvest_channels")
+        for op in self._channels:
+            op(stream)
 
     def candidates(self, stream):
-        g = self.g
-        _lib.check(_lib.lib().srn_harvest_candidates(
-            self.raw.data_ptr(), self.d_frames.data_ptr(), self.official.data_ptr(), self.cand.data_ptr(), self.B,
-            g["n_ch"], self.F1, g["n_base"], stream), "srn_harvest_candidates")
+        self._candidates(stream)
 
     def refine(self, stream):
-        g = self.g
-        _lib.check(_lib.lib().srn_harvest_refine(
-            self.y.data_ptr(), self.y.stride(0), self.d_ylens.data_ptr(), self.d_frames.data_ptr(),
-            self.cand.data_ptr(), self.refined.data_ptr(), self.score.data_ptr(), self.B, self.F1, g["n_cand"],
-            g["actual_fs"], self.f0_floor, self.f0_ceil, stream), "srn_harvest_refine")
+        self._refine(stream)
 
     def contour(self, stream):
-        g = self.g
-        _lib.check(_lib.lib().srn_harvest_contour(
-            self.refined.data_ptr(), self.score.data_ptr(), self.d_frames.data_ptr(), self.d_out_frames.data_ptr(),
-            self.smooth_coef.data_ptr(), self.cand2.data_ptr(), self.score2.data_ptr(), self.fbuf.data_ptr(),
-            self.pool.data_ptr(), self.pool_stride, self.sections.data_ptr(), self.sec_cap, self.status.data_ptr(),
-            self.f0.data_ptr(), self.f0.stride(0), self.B, self.F1, g["n_cand"], self.F, g["voice_range_minimum"],
-            self.frame_period, stream), "srn_harvest_contour")
+        self._contour(stream)
 
-    def run(self, x, stream):
+    def run(self, x, stream=None):
         self.decimate(x, stream)
         self.channels(stream)
         self.candidates(stream)
@@ -272,20 +277,14 @@ def harvest(x, fs, f0_floor=71.0, f0_ceil=800.0, frame_period=5.0, lengths=None)
     floors, ceils = _per_item(f0_floor, B, "f0_floor"), _per_item(f0_ceil, B, "f0_ceil")
     for pair in sorted(set(zip(floors, ceils))):
         _check(fs, pair[0], pair[1], frame_period)
-    if lengths is None:
-        lengths = (N,) * B
-    lengths = tuple(int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths))
-    if len(lengths) != B or min(lengths) < 1 or max(lengths) > N:
-        raise ValueError(f"harvest: lengths {lengths} must give {B} sample counts in [1, {N}]")
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in (torch.float32, torch.float64)):
-        raise RuntimeError("harvest: x must be a float32 or float64 CUDA (ROCm) tensor; there is no CPU path")
+    lengths = item_lengths(lengths, B, N, "harvest")
+    _require_cuda(x)
     one = x.ndim == 1
     xb = x.reshape(1, -1) if one else x
     if xb.stride(-1) != 1:
         xb = xb.contiguous()
     F = max(harvest_frames(n, fs, frame_period) for n in lengths)
     out = torch.zeros(B, F, dtype=torch.float64, device=x.device)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
     groups = {}
     for b in range(B):
         groups.setdefault((floors[b], ceils[b]), []).append(b)
@@ -298,7 +297,7 @@ def harvest(x, fs, f0_floor=71.0, f0_ceil=800.0, frame_period=5.0, lengths=None)
             xs = xb[idx[0]:idx[-1] + 1] if idx == list(range(idx[0], idx[-1] + 1)) else xb[idx]
             lens = tuple(lengths[b] for b in idx)
             key = (float(fs), lo, hi, float(frame_period), x.dtype == torch.float64)
-            f0 = _plan(x.device, len(idx), N, lens, key).run(xs, stream)
+            f0 = _plan(x.device, len(idx), N, lens, key).run(xs)
             out[idx, :f0.shape[1]] = f0
     t = np.arange(F) * frame_period / 1000.0
     return (out[0] if one else out), t
@@ -312,10 +311,8 @@ def extract_f0(audio, sampling_rate, minf0, maxf0, shiftms, lengths=None):
     if f0.ndim == 1:
         f0 = f0[:, None].clone()
         return f0, (f0 != 0).to(torch.float32)
-    N = audio.shape[1]
-    lengths = (N,) * f0.shape[0] if lengths is None else [int(v) for v in lengths]
     out = []
-    for b, n in enumerate(lengths):
+    for b, n in enumerate(item_lengths(lengths, *audio.shape, "harvest")):
         v = f0[b, :harvest_frames(n, sampling_rate, shiftms), None].clone()
         out.append((v, (v != 0).to(torch.float32)))
     return out

@@ -4,7 +4,7 @@ Tensors are torch CUDA fp32 tensors used as device memory only; every wrapper pa
 pointers, sizes and the current HIP stream.  All activations are channels-last (B, T, C).
 Nothing here computes on the host and nothing falls back to torch ops or to ``oracle/``.
 
-An op holds a reference to every tensor whose address it was built from (``ConvOp.kw``, ``ResUnitOp.kw``,
+An op holds a reference to every tensor whose address it was built from (the ``kw`` of the struct-parameter ops,
 ``CallOp.targs``, ``MultiCopyOp.srcs / dst``, ``TransposeMultiOp.entries``), so a plan's buffers live exactly as long as
 its op list does: plans keep no separate list of their buffers.
 """
@@ -16,7 +16,8 @@ import torch
 from . import _lib
 from ._lib import (ACT_LEAKY, ACT_MISH, ACT_NONE, ACT_SILU, POST_DIV, POST_LEAKY, POST_NONE, POST_RELU,  # noqa: F401
                    POST_TANH,
-                   RES_ADD, RES_AXPY, RES_NONE, SrnConvParams, SrnResUnitParams, check)
+                   RES_ADD, RES_AXPY, RES_NONE, SrnConvParams, SrnExcitationParams, SrnResUnitParams, SrnWorldParams,
+                   check)
 
 
 DEFAULT_PRECISION = _lib.PREC_FP32  # contraction arithmetic of ops built without an explicit precision
@@ -38,7 +39,8 @@ def _stream():
 
 
 def _ptr(x):
-    """tensor | (tensor, element_offset) | None -> raw device address (int) or None."""
+    """tensor | (tensor, element_offset) | None -> raw device address (int) or None.  The offset of the pair form
+    counts 4-byte elements (fp32 / int32 buffers); the float64 front-ends pass tensors or views, never pairs."""
     if x is None:
         return None
     if isinstance(x, tuple):
@@ -52,16 +54,39 @@ def _f32(t):
     return t
 
 
-class ConvOp:
-    """A prebuilt srn_conv_gemm call (parameters frozen, pointers borrowed from live tensors)."""
+class _StructOp:
+    """A prebuilt call of an entry point that takes one filled parameter struct and the stream: `p` the struct
+    (parameters frozen, pointers borrowed from live tensors), `kw` the keywords it was filled from -- kept for
+    introspection (tests emulate the C-ABI contract from it) and to pin the tensors -- and `name` the entry point."""
 
-    __slots__ = ("p", "kw", "_fn", "_wplanes")
+    __slots__ = ("p", "kw", "name", "_fn")
+    _profiled = False  # True: bench.py's PROFILE collects (start event, end event, op) around every launch
+
+    def __init__(self, name, kw):
+        self.name, self.kw, self._fn = name, kw, getattr(_lib.lib(), name)
+        self.p = self._fill(**kw)
+
+    def __call__(self, stream=None):
+        timed = self._profiled and PROFILE is not None and stream is None
+        if timed:  # bench.py: HIP events on the launch stream around the launch
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+        check(self._fn(ctypes.byref(self.p), stream if stream is not None else _stream()), self.name)
+        if timed:
+            e.record()
+            PROFILE.append((s, e, self))
+
+
+class ConvOp(_StructOp):
+    """A prebuilt srn_conv_gemm call."""
+
+    __slots__ = ("_wplanes",)
+    _profiled = True
 
     def __init__(self, **kw):
-        self.kw = kw  # kept for introspection (tests emulate the C-ABI contract from it) and to pin the tensors
-        self._build(**kw)
+        super().__init__("srn_conv_gemm", kw)
 
-    def _build(self, *, in0, w, out, n_batch, T_in, T_out, C_in, N, ld_in0, ldw, ld_out, taps=(0,), n_head=1,
+    def _fill(self, *, in0, w, out, n_batch, T_in, T_out, C_in, N, ld_in0, ldw, ld_out, taps=(0,), n_head=1,
                  in0_bs=0, in0_hs=0, in1=None, C_in0=0, in1_bs=0, ld_in1=0, C_w=0, w_bs=0, w_hs=0, w_nmajor=False,
                  bias=None, len_in=None, len_out=None, in_stride=1, reflect=False, pro_act=ACT_NONE, pro_slope=0.0,
                  alpha=1.0, beta=0.0, geglu=False, res=None, res_mode=RES_NONE, res_bs=0, res_hs=0, ld_res=0, res2=None,
@@ -92,8 +117,6 @@ class ConvOp:
         p.precision = int(DEFAULT_PRECISION if precision is None else precision)
         # _lib.ROUTE_*: kernel selection (testing / A-B timing); no_halo is its former name, same values
         p.route = int(route if no_halo is None else no_halo)
-        self.p = p
-        self._fn = _lib.lib().srn_conv_gemm
         self._wplanes = None
         if p.precision in (_lib.PREC_BF16X3, _lib.PREC_BF16X6):
             # static weights are split once, at plan-build time, into the bf16 plane images conv_fast.hip streams
@@ -108,17 +131,7 @@ class ConvOp:
             if o.is_cuda and self._fn and _lib.lib().srn_conv_gemm_workspace_bytes(ctypes.byref(p)) > 0:
                 ws = splitk_workspace(o.device)  # one per device: the ops of a plan run back to back on one stream
                 p.ws, p.ws_bytes = ws.data_ptr(), ws.numel()
-
-    def __call__(self, stream=None):
-        if PROFILE is not None and stream is None:
-            # bench.py: HIP events on the launch stream around every conv_gemm launch
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            check(self._fn(ctypes.byref(self.p), _stream()), "srn_conv_gemm")
-            e.record()
-            PROFILE.append((s, e, self))
-            return
-        check(self._fn(ctypes.byref(self.p), stream if stream is not None else _stream()), "srn_conv_gemm")
+        return p
 
 
 def splitk_workspace(device):
@@ -133,16 +146,16 @@ def splitk_workspace(device):
     return _SPLITK_WS[key]
 
 
-class ResUnitOp:
+class ResUnitOp(_StructOp):
     """A prebuilt srn_hifigan_resunit call: one fused HiFi-GAN residual unit (see include/serenade_hip.h)."""
 
-    __slots__ = ("p", "kw", "_fn", "_wplanes")
+    __slots__ = ("_wplanes",)
+    _profiled = True  # timed with the other contraction launches
 
     def __init__(self, **kw):
-        self.kw = kw
-        self._build(**kw)
+        super().__init__("srn_hifigan_resunit", kw)
 
-    def _build(self, *, x, w1, b1, w2, b2, out, n_batch, T, C, k, dilation, slope, res2=None, post_div=0.0,
+    def _fill(self, *, x, w1, b1, w2, b2, out, n_batch, T, C, k, dilation, slope, res2=None, post_div=0.0,
                precision=None, route=0):
         p = SrnResUnitParams()
         p.n_batch, p.T, p.C, p.k, p.dilation, p.slope = int(n_batch), int(T), int(C), int(k), int(dilation), float(slope)
@@ -157,18 +170,7 @@ class ResUnitOp:
         if p.precision == _lib.PREC_BF16X3 and w1.is_cuda:
             self._wplanes = (weight_planes(w1, C, k, C, k * C), weight_planes(w2, C, k, C, k * C))
             p.w1_hi, p.w2_hi = self._wplanes[0][0].data_ptr(), self._wplanes[1][0].data_ptr()
-        self.p = p
-        self._fn = _lib.lib().srn_hifigan_resunit
-
-    def __call__(self, stream=None):
-        if PROFILE is not None and stream is None:  # bench.py: timed with the other contraction launches
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            check(self._fn(ctypes.byref(self.p), _stream()), "srn_hifigan_resunit")
-            e.record()
-            PROFILE.append((s, e, self))
-            return
-        check(self._fn(ctypes.byref(self.p), stream if stream is not None else _stream()), "srn_hifigan_resunit")
+        return p
 
 
 class MultiCopyOp:
@@ -244,20 +246,22 @@ def tn_workspace(device, nbytes):
     return _TN_WS[key]
 
 
-class TnGemmOp:
+class TnGemmOp(_StructOp):
     """srn_tn_gemm (include/serenade_hip.h): out[z, m, j*N + n] = alpha * sum_{item,t} a[z,item,t,m] *
     b[z,item,t*stride + shifts[j], n].  a / b / out: tensor or (tensor, element offset).  len_b (int32, per item): rows
     of b at or past it read as zero; colsum (M,): alpha * the column sums of a (a conv's bias gradient), same launch."""
 
-    __slots__ = ("p", "kw", "_fn", "_ws")
+    __slots__ = ("_ws",)
 
     def __init__(self, *, a, b, out, n_items, T_a, T_b, M, N, lda, ldb, ldc, shifts=(0,), stride=1, n_batch=1,
                  n_head=1, a_bs=0, a_hs=0, a_is=0, b_bs=0, b_hs=0, b_is=0, out_bs=0, out_hs=0, alpha=1.0, n_inner=1,
                  a_is2=0, b_is2=0, len_b=None, colsum=None, route=0):
-        self.kw = dict(a=a, b=b, out=out, n_items=n_items, T_a=T_a, T_b=T_b, M=M, N=N, lda=lda, ldb=ldb, ldc=ldc,
-                       shifts=tuple(int(v) for v in shifts), stride=stride, n_batch=n_batch, n_head=n_head, a_bs=a_bs,
-                       a_hs=a_hs, a_is=a_is, b_bs=b_bs, b_hs=b_hs, b_is=b_is, out_bs=out_bs, out_hs=out_hs, alpha=alpha,
-                       n_inner=n_inner, a_is2=a_is2, b_is2=b_is2, len_b=len_b, colsum=colsum, route=route)
+        self.name, self._fn = "srn_tn_gemm", _lib.lib().srn_tn_gemm
+        self.kw = dict(
+            a=a, b=b, out=out, n_items=n_items, T_a=T_a, T_b=T_b, M=M, N=N, lda=lda, ldb=ldb, ldc=ldc,
+            shifts=tuple(int(v) for v in shifts), stride=stride, n_batch=n_batch, n_head=n_head, a_bs=a_bs, a_hs=a_hs,
+            a_is=a_is, b_bs=b_bs, b_hs=b_hs, b_is=b_is, out_bs=out_bs, out_hs=out_hs, alpha=alpha, n_inner=n_inner,
+            a_is2=a_is2, b_is2=b_is2, len_b=len_b, colsum=colsum, route=route)
         p = _lib.SrnTnGemmParams()
         p.n_batch, p.n_head, p.n_items, p.T_a, p.T_b = n_batch, n_head, n_items, T_a, T_b
         p.stride, p.n_shifts, p.M, p.N = stride, len(shifts), M, N
@@ -271,7 +275,6 @@ class TnGemmOp:
             raise TypeError("TnGemmOp: len_b must be int32")
         p.len_b, p.colsum = _ptr(len_b), _ptr(colsum)
         p.route = int(route)  # _lib.TN_ROUTE_GENERAL: the general kernel only (testing / A-B timing)
-        self._fn = _lib.lib().srn_tn_gemm
         need = int(_lib.lib().srn_tn_gemm_workspace_bytes(ctypes.byref(p)))
         self._ws = None
         if need:
@@ -280,8 +283,53 @@ class TnGemmOp:
             p.ws, p.ws_bytes = self._ws.data_ptr(), self._ws.numel()
         self.p = p
 
-    def __call__(self, stream=None):
-        check(self._fn(ctypes.byref(self.p), stream if stream is not None else _stream()), "srn_tn_gemm")
+
+class WorldOp(_StructOp):
+    """A prebuilt srn_world_cheaptrick / srn_world_d4c call (`entry`): float64 tensors x (B, N), f0 and t (B, F), their
+    valid counts x_len / n_frames (B,) int32, the FFT's twiddle table; out0 / out1 (B, F, ld) or None.  CheapTrick reads
+    q1 and f0_floor, D4C threshold and the band window."""
+
+    __slots__ = ()
+
+    def __init__(self, entry, **kw):
+        super().__init__(entry, kw)
+
+    def _fill(self, *, x, x_len, f0, t, n_frames, twiddle, fs, fft_size, unvoiced_db, q1=0.0, f0_floor=0.0,
+              threshold=0.0, band_window=None, n_bands=0, out0=None, out1=None):
+        p = SrnWorldParams()
+        p.n_batch, p.max_frames, p.fs, p.fft_size = f0.size(0), f0.size(1), int(fs), int(fft_size)
+        p.x, p.x_bs, p.x_len = _ptr(x), x.stride(0), _ptr(x_len)
+        p.f0, p.t, p.f_bs, p.n_frames, p.twiddle = _ptr(f0), _ptr(t), f0.stride(0), _ptr(n_frames), _ptr(twiddle)
+        p.q1, p.f0_floor, p.threshold, p.unvoiced_db = float(q1), float(f0_floor), float(threshold), float(unvoiced_db)
+        if band_window is not None:
+            p.band_window, p.band_window_len, p.n_bands = _ptr(band_window), band_window.numel(), int(n_bands)
+        if out0 is not None:
+            p.out0, p.out0_bs, p.ld_out0 = _ptr(out0), out0.stride(0), out0.size(-1)
+        if out1 is not None:
+            p.out1, p.out1_bs, p.ld_out1 = _ptr(out1), out1.stride(0), out1.size(-1)
+        return p
+
+
+class ExcitationOp(_StructOp):
+    """A prebuilt srn_sifigan_excitation call: f0 / df_f0 (B, F) float64 contours of the sine and of the dilated
+    factors, n_frames (B,) int32, phase_ws (B, F) float64 scratch, noise (B, F hop) fp32 or None, sine (B, 1, F hop) and
+    one dfs[i] (B, 1, F df_upsample[i]) per dense factor, fp32."""
+
+    __slots__ = ()
+
+    def __init__(self, **kw):
+        super().__init__("srn_sifigan_excitation", kw)
+
+    def _fill(self, *, f0, df_f0, n_frames, phase_ws, noise, sine, dfs, fs, hop, sine_amp, noise_amp, df_upsample,
+              dense_factors):
+        p = SrnExcitationParams()
+        p.n_batch, p.max_frames, p.fs, p.hop = f0.size(0), f0.size(1), int(fs), int(hop)
+        p.f0, p.df_f0, p.f_bs, p.n_frames = _ptr(f0), _ptr(df_f0), f0.stride(0), _ptr(n_frames)
+        p.phase_ws, p.noise, p.sine = _ptr(phase_ws), _ptr(noise), _ptr(sine)
+        p.sine_amp, p.noise_amp, p.n_df = sine_amp, noise_amp, len(dfs)
+        for i, d in enumerate(dfs):
+            p.dfs[i], p.df_upsample[i], p.dense_factors[i] = _ptr(d), df_upsample[i], dense_factors[i]
+        return p
 
 
 _WPLANES = {}  # (data_ptr, version, shape, ...) -> (planes, weight) bf16 weight planes, split once per weight VALUE
@@ -346,6 +394,11 @@ class CallOp:
 
     def __call__(self, stream=None):
         check(self._fn(*self._args, stream if stream is not None else _stream()), self.name)
+
+
+def call(name, *args):
+    """one-shot: build the CallOp and run it on the current stream"""
+    CallOp(name, args)()
 
 
 # ------------------------------------------------------------------ op builders (return CallOp)

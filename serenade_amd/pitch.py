@@ -25,8 +25,8 @@ import scipy.signal
 import scipy.stats
 import torch
 
-from . import _lib
-from .plan import lru_get
+from . import ops
+from .plan import dev_f64, dev_i32, item_lengths, lru_get
 
 __all__ = ["pyin", "pyin_geometry", "pyin_frames"]
 
@@ -124,7 +124,15 @@ def prior_tables(n_thresholds, beta_parameters, boltzmann_parameter, no_trough_p
     return thr[1:], beta_probs, fact, bexp, no_trough
 
 
+def _require_cuda(wave):
+    if not (isinstance(wave, torch.Tensor) and wave.is_cuda and wave.dtype == torch.float32 and wave.ndim in (1, 2)):
+        raise RuntimeError("pyin: wave must be a (B, N) or (N,) float32 CUDA (ROCm) tensor; there is no CPU path")
+
+
 class _PyinPlan:
+    """tables, buffers and the prebuilt Viterbi op of one (device, B, N, lengths, parameters) call; only the
+    observation kernel reads the caller's wave, so only its op is built per call"""
+
     def __init__(self, dev, B, N, lengths, key):
         (sr, fmin, fmax, frame_length, win_length, hop_length, n_thresholds, beta_parameters, boltzmann_parameter,
          resolution, max_transition_rate, switch_prob, no_trough_prob, fill_na, center) = key
@@ -143,11 +151,10 @@ class _PyinPlan:
             raise ValueError(f"pyin: an item is shorter than frame_length={frame_length} (center=False)")
         self.B, self.N, self.T = B, N, max(frames)
         self.frames = torch.tensor(frames, dtype=torch.int64)
-        self.sr, self.fmin, self.fill_na = float(sr), float(fmin), fill_na
+        self.sr, self.fmin = float(sr), float(fmin)
         self.frame_length, self.n_thresholds = frame_length, n_thresholds
-        i32 = lambda a: torch.tensor(a, dtype=torch.int32, device=dev)
-        f64 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-        self.d_lens, self.d_frames = i32(list(lengths)), i32(frames)
+        f64 = lambda a: dev_f64(a, dev)
+        self.d_lens, self.d_frames = dev_i32(lengths, dev), dev_i32(frames, dev)
         thr, beta_probs, fact, bexp, no_trough = prior_tables(n_thresholds, beta_parameters, boltzmann_parameter,
                                                               no_trough_prob, nf)
         self.tabs = [f64(a) for a in (thr, beta_probs, fact, bexp, no_trough)]
@@ -167,22 +174,20 @@ class _PyinPlan:
         self.f0 = torch.empty(B, T, dtype=torch.float64, device=dev)
         self.flag = torch.empty(B, T, dtype=torch.uint8, device=dev)
 
+        fill = fill_na is not None
+        self._viterbi = ops.CallOp("srn_pyin_viterbi", (
+            self.obs, self.vp, self.d_frames, self.band, self.log_p_init, self.freqs, self.log_tiny,
+            float(fill_na) if fill else 0.0, int(fill), self.ptr, self.states, self.f0, self.flag, B, T, n, g["width"]))
+
     def observe(self, x, stream):
-        g, lib = self.g, _lib.lib()
-        _lib.check(lib.srn_pyin_observe(
-            x.data_ptr(), x.stride(0), self.d_lens.data_ptr(), self.d_frames.data_ptr(),
-            *[t.data_ptr() for t in self.tabs], self.obs.data_ptr(), self.vp.data_ptr(), self.B, self.N, self.T,
+        g = self.g
+        ops.CallOp("srn_pyin_observe", (
+            x, x.stride(0), self.d_lens, self.d_frames, *self.tabs, self.obs, self.vp, self.B, self.N, self.T,
             self.frame_length, g["win_length"], g["hop_length"], self.pad, g["min_period"], g["max_period"],
-            self.n_thresholds, self.sr, self.fmin, float(12 * g["nbps"]), g["n_bins"], stream), "srn_pyin_observe")
+            self.n_thresholds, self.sr, self.fmin, float(12 * g["nbps"]), g["n_bins"]))(stream)
 
     def viterbi(self, stream):
-        g, lib = self.g, _lib.lib()
-        fill = self.fill_na is not None
-        _lib.check(lib.srn_pyin_viterbi(
-            self.obs.data_ptr(), self.vp.data_ptr(), self.d_frames.data_ptr(), self.band.data_ptr(),
-            self.log_p_init.data_ptr(), self.freqs.data_ptr(), self.log_tiny, float(self.fill_na) if fill else 0.0,
-            int(fill), self.ptr.data_ptr(), self.states.data_ptr(), self.f0.data_ptr(), self.flag.data_ptr(),
-            self.B, self.T, g["n_bins"], g["width"], stream), "srn_pyin_viterbi")
+        self._viterbi(stream)
 
 
 _PLANS = {}
@@ -204,26 +209,20 @@ def pyin(wave, lengths=None, *, fmin, fmax, sr=22050, frame_length=2048, win_len
     if hop_length is None:
         hop_length = frame_length // 4
     _check(sr, fmin, fmax, frame_length, win_length, hop_length, n_thresholds, resolution, center, pad_mode)
-    if not (isinstance(wave, torch.Tensor) and wave.is_cuda and wave.dtype == torch.float32 and wave.ndim in (1, 2)):
-        raise RuntimeError("pyin: wave must be a (B, N) or (N,) float32 CUDA (ROCm) tensor; there is no CPU path")
+    _require_cuda(wave)
     one = wave.ndim == 1
     x = wave.reshape(1, -1) if one else wave
     if x.stride(-1) != 1:
         x = x.contiguous()
     B, N = x.shape
-    if lengths is None:
-        lengths = (N,) * B
-    lengths = tuple(int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths))
-    if len(lengths) != B or min(lengths) < 1 or max(lengths) > N:
-        raise ValueError(f"pyin: lengths {lengths} must give {B} sample counts in [1, {N}]")
+    lengths = item_lengths(lengths, B, N, "pyin")
     fill = None if fill_na is None else float(fill_na)
     key = (sr, float(fmin), float(fmax), frame_length, win_length, hop_length, n_thresholds,
            tuple(beta_parameters), boltzmann_parameter, resolution, max_transition_rate, switch_prob, no_trough_prob,
            "nan" if fill is not None and math.isnan(fill) else fill, bool(center))  # NaN != NaN: keyed by name
     plan = _plan(x.device, B, N, lengths, key)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    plan.observe(x, stream)
-    plan.viterbi(stream)
+    plan.observe(x, None)
+    plan.viterbi(None)
     f0, flag, vp = plan.f0.clone(), plan.flag.bool(), plan.vp.clone()
     if one:
         return f0[0], flag[0], vp[0], plan.frames.clone()

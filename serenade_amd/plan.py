@@ -29,6 +29,16 @@ def dev_f32(t, dev):
     return r.clone() if r.data_ptr() == t.data_ptr() else r
 
 
+def dev_i32(values, dev):
+    """int32 device copy of a sequence of integers (per-item counts, offset tables)"""
+    return torch.tensor([int(v) for v in values], dtype=torch.int32, device=dev)
+
+
+def dev_f64(a, dev):
+    """float64 device copy of a host table (array-like)"""
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+
+
 def lru_get(cache, key, capacity, make):
     """dict used as an LRU (insertion order = recency): a hit moves the entry to the back, a miss evicts only the
     least recently used entries beyond `capacity` -- never the plan in use (the B = 1 decode loop sees a new length
@@ -121,6 +131,17 @@ def attention_ops(qkv, Vt, S, out, lens, B, H, hd, T, precision):
 
 
 # ---------------------------------------------------------------------------------------------- front-end plumbing
+def item_lengths(lengths, B, N, what):
+    """the per-item sample counts of a (B, N) batch as a tuple of ints: `lengths` (tensor, numpy or sequence), or N for
+    every item when it is None.  ValueError unless there are B values in [1, N]."""
+    if lengths is None:
+        return (N,) * B
+    lens = tuple(int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths))
+    if len(lens) != B or min(lens) < 1 or max(lens) > N:
+        raise ValueError(f"{what}: lengths {lens} must give {B} sample counts in [1, {N}]")
+    return lens
+
+
 def wave_batch(wave, lengths, device, what, allow_channel_dim=False):
     """(n,) or (B, n) waveform(s) -- (B, 1, n) too with allow_channel_dim -- as a tensor or numpy, and optional
     per-item sample counts -> ((B, n) fp32 tensor on the GPU, [int lengths]).  A CPU input is uploaded to `device`."""
@@ -141,11 +162,7 @@ def wave_batch(wave, lengths, device, what, allow_channel_dim=False):
             raise RuntimeError(f"{what} needs a CUDA (ROCm) device; there is no CPU fallback")
         a = a.to(device)
     a = a.to(torch.float32)
-    B, n = a.shape
-    lens = [n] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-    if len(lens) != B or max(lens) > n or min(lens) < 1:
-        raise ValueError(f"{what}: lengths {lens} do not fit a batch of {B} x {n} samples")
-    return a, lens
+    return a, list(item_lengths(lengths, *a.shape, what))
 
 
 def check_state(what, state, want, ignored=()):

@@ -15,11 +15,12 @@ prior_loss -> `backward()` -> DDP gradient all-reduce over NCCL -> `clip_grad_no
 Division of labour.  GEMM-shaped gradients that contract over channels -- dgrad of every conv / projection (a conv of
 dY with the tap-reversed, transposed weights), dP = dO V^T and dQ = dS K of attention -- are `srn_conv_gemm` launches;
 row / column reductions and activations (GroupNorm+Mish, LayerNorm / SpeakerAdapter, softmax, GEGLU) are the kernels of
-csrc/train.hip.  Gradients that contract over TIME (wgrad = dY^T X, dV = P^T dO, dK = dS^T Q) are plain transposed-A
-GEMMs and go to rocBLAS through `torch.matmul` (the library-GEMM case).  torch autograd is the tape; mask multiplies,
-concatenations, LeakyReLU / dropout, weight-norm folding, the (B, 2048) time-embedding activations and the scalar loss
-reductions are torch ops on the same device.  The GST style encoder (0.8 GFLOP of a ~1.3 TFLOP step: 3x3 Conv2d +
-train-mode BatchNorm2d, a 16-step GRU, 50-token attention) runs on torch's GPU ops in both directions.  Dropout uses
+csrc/train.hip.  Gradients that contract over TIME (wgrad = dY^T X, dV = P^T dO, dK = dS^T Q) are transposed-A GEMMs
+and are `srn_tn_gemm` launches (ops.TnGemmOp).  torch autograd is the tape; mask multiplies, concatenations,
+LeakyReLU / dropout, weight-norm folding, the (B, 2048) time-embedding activations and the scalar loss reductions are
+torch ops on the same device.  The GST style encoder (0.8 GFLOP of a ~1.3 TFLOP step: 3x3 Conv2d + train-mode
+BatchNorm2d, a 16-step GRU, 50-token attention) runs on the same contractions plus the srn_bn_relu_*, srn_gru_train_*
+and srn_token_attn_* kernels in both directions (`TrainSerenade.gst`).  Dropout uses
 torch's generator (the reference's draws cannot be reproduced); parity tests run with dropout off against the
 reference's own gradients (tests/golden/train_grads_L45.npz, train_full_T64.npz).
 """
@@ -35,8 +36,7 @@ from .plan import require_cuda as _require_cuda, rup
 __all__ = ["Estimator", "TrainSerenade", "ParamStore", "GraphedStep", "MultiStepLR", "save_checkpoint", "load_checkpoint", "GradSync", "AdamW", "cfm_loss", "conv1d", "gn_mish", "row_ln", "attention_core", "geglu"]
 
 
-def _call(name, *args):
-    ops.CallOp(name, args)()
+_call = ops.call
 
 
 NORM_BWD_ROWS = 8  # rows per chunk of partial sums in the LayerNorm / GroupNorm backward kernels (srn_rowln_chunks, srn_gn_chunks)
@@ -979,10 +979,10 @@ class TrainSerenade:
 
       * estimator: `Estimator` above (HIP forward and backward);
       * content encoder `Conv1dResnet` (serenade.py:282-296,310-376): weight-norm folded by torch ops, reflection
-        padding as a row gather, every conv through `conv1d` (HIP forward, dgrad; rocBLAS wgrad), LeakyReLU in torch;
+        padding as a row gather, every conv through `conv1d` (HIP forward, dgrad and wgrad), LeakyReLU in torch;
       * GST style encoder (modules/gst/style_encoder.py): six 3x3 stride-2 Conv2d + train-mode BatchNorm2d + ReLU, a
-        GRU over T_ref / 64 steps and the 50-token attention -- 0.8 GFLOP of the step's ~1.3 TFLOP -- run on
-        torch's GPU ops (MIOpen / rocBLAS) in both directions: the library path, not hand-written kernels.
+        GRU over T_ref / 64 steps and the 50-token attention -- 0.8 GFLOP of the step's ~1.3 TFLOP -- run on the
+        project's own kernels in both directions (`gst` below).
     BatchNorm running statistics are updated like nn.BatchNorm2d (momentum 0.1) in `self.buffers`."""
 
     def __init__(self, state_dict, device, dropout=0.05, mask_size=(0.1, 0.5), output_dim=80):

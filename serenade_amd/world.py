@@ -22,16 +22,15 @@ Parity: pyworld / pysptk / sifigan are not under /root/reference and not install
 `convert_continuos_f0` and `match_length` (pinned by tests/golden/postproc_f0.npz) is **parity unpinned** and is checked
 against the restatement of the published algorithms in oracle/world_oracle.py (tests only).
 """
-import ctypes
 import math
 
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import SrnExcitationParams, SrnWorldParams, check
-from .ops import _stream
-from .plan import require_cuda as _require_cuda
+from . import ops
+# preprocessing's Harvest (preprocess.py:485-493) lives in harvest.py; stage 9 below keeps only its frame count
+from .harvest import extract_f0, harvest, harvest_frames as harvest_frame_count, nuttall_window  # noqa: F401
+from .plan import dev_f64, dev_i32 as _i32, item_lengths, require_cuda as _require_cuda
 
 __all__ = ["ALPHA", "harvest_frame_count", "harvest_time_axis", "cheaptrick", "cheaptrick_fft_size",
            "d4c_band_aperiodicity", "sp2mc", "match_length", "convert_continuos_f0", "Analyzer", "harvest",
@@ -46,11 +45,6 @@ _UNVOICED_DB = float(20 * np.log10(1.0 - 1e-12))
 
 
 # ------------------------------------------------------------------------------------------------ sizes (host)
-def harvest_frame_count(x_length, fs, frame_period=5.0):
-    """number of frames `pw.harvest` returns (WORLD GetSamplesForHarvest); the reference keeps nothing else of it."""
-    return int(1000.0 * x_length / fs / frame_period) + 1
-
-
 def harvest_time_axis(x_length, fs, frame_period=5.0):
     """temporal positions `t` of `pw.harvest` in seconds (float64 numpy)."""
     return np.arange(harvest_frame_count(x_length, fs, frame_period)) * frame_period / 1000.0
@@ -76,7 +70,7 @@ _TABLES = {}
 def _table(dev, key, make):
     k = (dev.index, key)
     if k not in _TABLES:
-        _TABLES[k] = torch.from_numpy(np.ascontiguousarray(make(), dtype=np.float64)).to(dev)
+        _TABLES[k] = dev_f64(make(), dev)
     return _TABLES[k]
 
 
@@ -88,11 +82,7 @@ def _twiddles(dev, n):
 
 
 def _nuttall(dev, n):
-    def make():
-        tmp = np.arange(n) / (n - 1.0)
-        return (0.355768 - 0.487396 * np.cos(2.0 * np.pi * tmp) + 0.144232 * np.cos(4.0 * np.pi * tmp)
-                - 0.012604 * np.cos(6.0 * np.pi * tmp))
-    return _table(dev, ("nuttall", n), make)
+    return _table(dev, ("nuttall", n), lambda: nuttall_window(n))
 
 
 def _freqt_matrix(m1, order, alpha):
@@ -129,11 +119,7 @@ def _sp2mc_matrix(dev, n_bins, order, alpha, from_cepstrum):
 def _as_f64(v, dev):
     if torch.is_tensor(v):
         return v.to(device=dev, dtype=_F64).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(dev)
-
-
-def _i32(values, dev):
-    return torch.tensor([int(v) for v in values], dtype=torch.int32, device=dev)
+    return dev_f64(v, dev)
 
 
 def _batch_view(x, f0, t):
@@ -151,15 +137,9 @@ def _batch_view(x, f0, t):
     return x, f0, t, single
 
 
-def _world_params(x, x_len, f0, t, n_frames, fs, fft_size):
-    B, F = f0.shape
-    p = SrnWorldParams()
-    p.n_batch, p.max_frames, p.fs, p.fft_size = B, F, int(fs), int(fft_size)
-    p.x, p.x_bs, p.x_len = x.data_ptr(), x.stride(0), x_len.data_ptr()
-    p.f0, p.t, p.f_bs, p.n_frames = f0.data_ptr(), t.data_ptr(), f0.stride(0), n_frames.data_ptr()
-    p.twiddle = _twiddles(x.device, fft_size).data_ptr()
-    p.unvoiced_db = _UNVOICED_DB
-    return p
+def _world_op(entry, x, x_len, f0, t, n_frames, fs, fft_size, **kw):
+    return ops.WorldOp(entry, x=x, x_len=x_len, f0=f0, t=t, n_frames=n_frames, twiddle=_twiddles(x.device, fft_size),
+                       fs=fs, fft_size=fft_size, unvoiced_db=_UNVOICED_DB, **kw)
 
 
 def _check_f0(f0, fs):
@@ -178,17 +158,12 @@ def _cheaptrick_raw(x, x_len, f0, t, n_frames, fs, q1, f0_floor, fft_size, want_
     dev = x.device
     B, F = f0.shape
     nb = fft_size // 2 + 1
-    p = _world_params(x, x_len, f0, t, n_frames, fs, fft_size)
-    p.q1 = float(q1)
-    p.f0_floor = 3.0 * fs / (fft_size - 3.0)  # GetF0FloorForCheapTrick: the lowest F0 the window still fits
     del f0_floor  # pyworld's argument only sizes the transform
     sp = torch.empty(B, F, nb, dtype=_F64, device=dev) if want_sp else None
     ceps = torch.empty(B, F, nb, dtype=_F64, device=dev) if want_ceps else None
-    if sp is not None:
-        p.out0, p.out0_bs, p.ld_out0 = sp.data_ptr(), sp.stride(0), nb
-    if ceps is not None:
-        p.out1, p.out1_bs, p.ld_out1 = ceps.data_ptr(), ceps.stride(0), nb
-    check(_lib.lib().srn_world_cheaptrick(ctypes.byref(p), _stream()), "srn_world_cheaptrick")
+    # f0_floor: GetF0FloorForCheapTrick, the lowest F0 the window still fits
+    _world_op("srn_world_cheaptrick", x, x_len, f0, t, n_frames, fs, fft_size, q1=q1,
+              f0_floor=3.0 * fs / (fft_size - 3.0), out0=sp, out1=ceps)()
     return sp, ceps
 
 
@@ -211,13 +186,9 @@ def _d4c_raw(x, x_len, f0, t, n_frames, fs, threshold):
     N = _d4c_fft_size(fs)
     nb = _n_bands(fs)
     wl = int(3000.0 * N / fs) * 2 + 1
-    p = _world_params(x, x_len, f0, t, n_frames, fs, N)
-    p.threshold = float(threshold)
-    win = _nuttall(dev, wl)
-    p.band_window, p.band_window_len, p.n_bands = win.data_ptr(), wl, nb
     bap = torch.empty(B, F, nb, dtype=_F64, device=dev)
-    p.out0, p.out0_bs, p.ld_out0 = bap.data_ptr(), bap.stride(0), nb
-    check(_lib.lib().srn_world_d4c(ctypes.byref(p), _stream()), "srn_world_d4c")
+    _world_op("srn_world_d4c", x, x_len, f0, t, n_frames, fs, N, threshold=threshold, band_window=_nuttall(dev, wl),
+              n_bands=nb, out0=bap)()
     return bap
 
 
@@ -238,8 +209,7 @@ def _project(inp, mat_t, take_log):
     rows, K = inp.numel() // inp.size(-1), inp.size(-1)
     n_out = mat_t.size(1)
     out = torch.empty(*inp.shape[:-1], n_out, dtype=_F64, device=inp.device)
-    check(_lib.lib().srn_world_project(inp.data_ptr(), rows, K, K, mat_t.data_ptr(), n_out, int(take_log),
-                                       out.data_ptr(), n_out, _stream()), "srn_world_project")
+    ops.call("srn_world_project", inp, rows, K, K, mat_t, n_out, int(take_log), out, n_out)
     return out
 
 
@@ -259,10 +229,8 @@ def match_length(f0_list, n_out, device):
         buf[i, :n_in[i]] = np.asarray(f, dtype=np.float64).ravel()
     src = torch.from_numpy(buf).to(device)
     out = torch.zeros(B, max(n_out), dtype=_F64, device=device)
-    n_in_d, n_out_d = _i32(n_in, device), _i32(n_out, device)  # named: the pointers must outlive the launch call
-    check(_lib.lib().srn_f0_match_length(src.data_ptr(), src.stride(0), n_in_d.data_ptr(), out.data_ptr(),
-                                         out.stride(0), n_out_d.data_ptr(), B, max(n_out), _stream()),
-          "srn_f0_match_length")
+    ops.call("srn_f0_match_length", src, src.stride(0), _i32(n_in, device), out, out.stride(0), _i32(n_out, device), B,
+             max(n_out))
     return out
 
 
@@ -271,8 +239,7 @@ def _cont_f0_raw(f0, n_frames):
     cf0 = torch.zeros_like(f0)
     uv = torch.zeros(B, F, dtype=torch.float32, device=f0.device)
     ok = torch.zeros(B, dtype=torch.int32, device=f0.device)
-    check(_lib.lib().srn_cont_f0(f0.data_ptr(), f0.stride(0), n_frames.data_ptr(), cf0.data_ptr(), uv.data_ptr(),
-                                 ok.data_ptr(), B, _stream()), "srn_cont_f0")
+    ops.call("srn_cont_f0", f0, f0.stride(0), n_frames, cf0, uv, ok, B)
     return uv, cf0, ok
 
 
@@ -322,16 +289,13 @@ class Analyzer:
         dev = wave.device
         wave = wave.to(torch.float32).reshape(len(f0_list), -1).contiguous()
         B = wave.size(0)
-        lengths = [int(v) for v in lengths]
-        if len(lengths) != B or min(lengths) < 1 or max(lengths) > wave.size(1):
-            raise ValueError(f"lengths {lengths} do not describe a (B = {B}, N = {wave.size(1)}) batch of waveforms")
+        lengths = item_lengths(lengths, B, wave.size(1), "Analyzer.features")
         if any(np.asarray(f).size < 1 for f in f0_list):
             raise ValueError("every item needs an F0 contour of at least one frame")
         n_frames = [harvest_frame_count(n, self.fs, self.frame_period) for n in lengths]
         F = max(n_frames)
         x = torch.empty(wave.shape, dtype=_F64, device=dev)
-        check(_lib.lib().srn_wave_to_f64(wave.data_ptr(), x.data_ptr(), wave.numel(), int(self.pcm16), _stream()),
-              "srn_wave_to_f64")
+        ops.call("srn_wave_to_f64", wave, x, wave.numel(), int(self.pcm16))
         f0 = match_length(f0_list, n_frames, dev)
         _check_f0(f0, self.fs)
         t = torch.from_numpy(np.arange(F) * self.frame_period / 1000.0).to(dev)[None].expand(B, F).contiguous()
@@ -344,10 +308,7 @@ class Analyzer:
         mean = scale = None
         if self._stats is not None:
             mean, scale = (_table(dev, ("stats", i, self._stats[i].tobytes()), lambda i=i: self._stats[i]) for i in (0, 1))
-        check(_lib.lib().srn_world_pack_features(mcep.data_ptr(), mcep.size(-1), bap.data_ptr(), bap.size(-1),
-                                                 mean.data_ptr() if mean is not None else None,
-                                                 scale.data_ptr() if scale is not None else None,
-                                                 c.data_ptr(), B * F, nc, _stream()), "srn_world_pack_features")
+        ops.call("srn_world_pack_features", mcep, mcep.size(-1), bap, bap.size(-1), mean, scale, c, B * F, nc)
         uv, cf0, ok = _cont_f0_raw(f0, nf)
         return dict(c=c.transpose(1, 2), mcep=mcep, bap=bap, f0=f0, cf0=cf0, uv=uv, ok=ok, n_frames=n_frames, nf=nf)
 
@@ -366,23 +327,13 @@ class Analyzer:
         sine = torch.zeros(B, 1, n, dtype=torch.float32, device=dev)
         dfs = [torch.zeros(B, 1, F * u, dtype=torch.float32, device=dev) for u in self.upsample]
         phase = torch.empty(B, F, dtype=_F64, device=dev)
-        p = SrnExcitationParams()
-        p.n_batch, p.max_frames, p.fs, p.hop = B, F, self.fs, self.hop
-        p.f0 = (cf0 if self.sine_f0_type == "cf0" else f0).data_ptr()
-        p.df_f0 = (cf0 if self.df_f0_type == "cf0" else f0).data_ptr()
-        p.f_bs, p.n_frames, p.phase_ws = f0.stride(0), nf.data_ptr(), phase.data_ptr()
-        p.noise = noise.data_ptr() if noise is not None else None
-        p.sine, p.sine_amp, p.noise_amp, p.n_df = sine.data_ptr(), self.sine_amp, self.noise_amp, len(dfs)
-        for i, d in enumerate(dfs):
-            p.dfs[i], p.df_upsample[i], p.dense_factors[i] = d.data_ptr(), self.upsample[i], self.dense_factors[i]
-        check(_lib.lib().srn_sifigan_excitation(ctypes.byref(p), _stream()), "srn_sifigan_excitation")
+        ops.ExcitationOp(f0=cf0 if self.sine_f0_type == "cf0" else f0, df_f0=cf0 if self.df_f0_type == "cf0" else f0,
+                         n_frames=nf, phase_ws=phase, noise=noise, sine=sine, dfs=dfs, fs=self.fs, hop=self.hop,
+                         sine_amp=self.sine_amp, noise_amp=self.noise_amp, df_upsample=self.upsample,
+                         dense_factors=self.dense_factors)()
         return sine, dfs
 
     def __call__(self, wave, lengths, f0_list, noise=None, generator=None):
         feats = self.features(wave, lengths, f0_list)
         in_signal, dfs = self.excitation(feats, noise, generator)
         return in_signal, feats["c"], dfs, feats
-
-
-# preprocessing's Harvest (preprocess.py:485-493) lives in harvest.py; stage 9 above keeps only its frame count
-from .harvest import extract_f0, harvest  # noqa: E402,F401

@@ -607,7 +607,7 @@ class installed:
             for k, v in dict(stride=1, n_batch=1, n_head=1, a_bs=0, a_hs=0, a_is=0, b_bs=0, b_hs=0, b_is=0, out_bs=0,
                              out_hs=0, alpha=1.0, n_inner=1, a_is2=0, b_is2=0, len_b=None, colsum=None).items():
                 kw.setdefault(k, v)
-            self_.kw = kw
+            self_.name, self_.kw = "srn_tn_gemm", kw
         ops.TnGemmOp.__init__ = tn_init
         ops.ConvOp.__call__ = lambda self_, stream=None: emul_conv(self_.kw)
         ops.ResUnitOp.__call__ = lambda self_, stream=None: emul_resunit(self_.kw)

@@ -3,10 +3,14 @@ serialised in order -- entry point, every argument, every operand as (buffer ord
 the digest is compared with the committed table tests/plan_ops.json.  A change of a stride, an offset, a default or of
 which buffer an op reads or writes changes the digest; allocation order and addresses do not.
 
-How one op serialises: its class, the C-ABI entry point and every argument of `op.kw` (ConvOp, ResUnitOp; keys sorted) or
-`op.targs` (CallOp).  A tensor or a (tensor, element offset) pair becomes [ordinal of the first appearance of its storage
+The front-ends that build part of their launches per call (pYIN, Harvest, the WORLD analysis) are digested through their
+public entry points instead: run on CPU tensors with the device guards lifted and every op's `__call__` replaced by a
+recorder, the same mechanism as `_emulator.installed`.
+
+How one op serialises: its class, the C-ABI entry point and every argument of `op.kw` (the struct-parameter ops; keys
+sorted) or `op.targs` (CallOp).  A tensor or a (tensor, element offset) pair becomes [ordinal of the first appearance of its storage
 in this op list, element offset including the storage offset, the storage's element count, dtype]; scalars go by value,
-ranges and tuples as lists.  ConvOp and ResUnitOp also write the non-pointer fields of the filled params struct, so
+ranges and tuples as lists.  The struct-parameter ops also write the non-pointer fields of the filled params struct, so
 resolved defaults (the precision, the tap table) are covered.
 
     python -m tests.test_plan_ops          # prints the table for tests/plan_ops.json
@@ -19,18 +23,19 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 import torch
 
 import serenade_amd
-from serenade_amd import _shapes, contentvec, features, models, ops, plan, sifigan, transcriber, vocoder
+from serenade_amd import (_shapes, contentvec, features, harvest, models, ops, pitch, plan, sifigan, transcriber, vocoder,
+                          world)
 from serenade_amd.utils.synth import HIFIGAN_PARAMS, SERENADE_PARAMS, fill_state_dict
 from tests import _emulator
 from tests._weights import serenade_weights
 from tests.test_sifigan import SMALL as SIFIGAN_SMALL
 
 TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "plan_ops.json")
-ENTRY = {ops.ConvOp: "srn_conv_gemm", ops.ResUnitOp: "srn_hifigan_resunit"}
 CPU = torch.device("cpu")
 # test_contentvec_host.SMALL (that module skips itself without transformers, so it is not imported here)
 CVEC_SMALL = dict(hidden_size=32, num_hidden_layers=1, num_attention_heads=2, intermediate_size=64, conv_dim=[16] * 7,
@@ -59,7 +64,7 @@ def _struct(p):
     """the non-pointer fields of a filled params struct"""
     out = {}
     for name, ctype in p._fields_:
-        if ctype is ctypes.c_void_p:
+        if ctype is ctypes.c_void_p or getattr(ctype, "_type_", None) is ctypes.c_void_p:  # pointers, arrays of them
             continue
         v = getattr(p, name)
         out[name] = list(v) if isinstance(v, ctypes.Array) else v
@@ -74,7 +79,7 @@ def serialise(op_list):
             out.append(["CallOp", op.name, [_value(a, storages) for a in op.targs]])
         else:
             args = {k: _value(op.kw[k], storages) for k in sorted(op.kw)}
-            out.append([type(op).__name__, ENTRY[type(op)], args, _struct(op.p)])
+            out.append([type(op).__name__, op.name, args, _struct(op.p)])
     return out
 
 
@@ -171,6 +176,97 @@ def _transcriber():
     return transcriber._Plan(m, CPU, 2, 32000, [32000, 23111]).ops
 
 
+# ---------------------------------------------------------------------------------------------- the front-ends
+@contextlib.contextmanager
+def _recorded():
+    """the ops the front-ends run, in order, instead of their launches (CPU tensors pass the lifted guards)"""
+    classes, mods = (ops.CallOp, ops.WorldOp, ops.ExcitationOp), (world, pitch, harvest)
+    guards = [m._require_cuda for m in mods]
+    run_call, ran = ops.CallOp.__call__, []
+    for c in classes:
+        c.__call__ = lambda self_, stream=None: ran.append(self_)
+    for m in mods:
+        m._require_cuda = lambda *a, **k: None
+        getattr(m, "_PLANS", {}).clear()  # plans are keyed without the budgets lowered below
+    try:
+        yield ran
+    finally:
+        ops.CallOp.__call__ = run_call
+        del ops.WorldOp.__call__, ops.ExcitationOp.__call__  # inherited from the base again
+        for m, guard in zip(mods, guards):
+            m._require_cuda = guard
+            getattr(m, "_PLANS", {}).clear()
+
+
+def _names(ol):
+    return [op.name for op in ol]
+
+
+def _pyin():
+    with _recorded() as ol:
+        pitch.pyin(torch.zeros(2, 8000), [8000, 5111], sr=16000, fmin=65, fmax=2093, frame_length=1024, hop_length=320)
+    assert _names(ol) == ["srn_pyin_observe", "srn_pyin_viterbi"]
+    return ol
+
+
+def _harvest(budget, value, n_ops, *args, **kw):
+    """harvest.harvest with one of the module's budgets lowered (as _contentvec_head_chunks lowers S_BUDGET)"""
+    saved = getattr(harvest, budget)
+    setattr(harvest, budget, saved if value is None else value)
+    try:
+        with _recorded() as ol:
+            harvest.harvest(*args, **kw)
+    finally:
+        setattr(harvest, budget, saved)
+    assert len(ol) == n_ops
+    return ol
+
+
+def _harvest_24k():
+    """the event scratch holds 60 of the 152 channels: three srn_harvest_channels launches"""
+    ev_cap = -(-6000 // 3) // 2
+    ol = _harvest("EVENT_BUDGET", 60 * 2 * 4 * ev_cap * 8, 1 + 3 + 3, torch.zeros(2, 6000), 24000, 71.0, 800.0, 5.0,
+                  lengths=[6000, 4111])
+    assert [op.targs[13:15] for op in ol[1:4]] == [(0, 60), (60, 60), (120, 32)]  # ch0, channels of the launch
+    return ol
+
+
+def _harvest_8k():
+    ol = _harvest("EVENT_BUDGET", None, 5, torch.zeros(2, 3000, dtype=torch.float64), 8000, lengths=[3000, 2111])
+    assert ol[0].targs[1] == 1 and ol[0].targs[5] is None  # float64 input, no decimation workspace
+    return ol
+
+
+def _harvest_two_floors():
+    """the workspace budget holds one item: the two items of the first group run as two plans"""
+    one = harvest._sizes(harvest.harvest_geometry(24000, 71.0, 800.0), [4000, 3111], 24000)[4]
+    ol = _harvest("WORKSPACE_BUDGET", one, 3 * 5, torch.zeros(3, 4000), 24000, f0_floor=[71, 71, 90],
+                  lengths=[4000, 3111, 3500])
+    assert [op.targs[9] for op in ol[::5]] == [1, 1, 1] and [op.targs[-2] for op in ol[1::5]] == [71.0, 71.0, 90.0]
+    return ol
+
+
+def _world_analyzer():
+    with _recorded() as ol:
+        world.Analyzer()(torch.zeros(2, 4800), [4800, 3333], [np.full(30, 220.0), np.full(21, 180.0)],
+                         noise=torch.zeros(2, 1, 41 * 120))
+    assert _names(ol) == ["srn_wave_to_f64", "srn_f0_match_length", "srn_world_cheaptrick", "srn_world_project",
+                          "srn_world_d4c", "srn_world_pack_features", "srn_cont_f0", "srn_sifigan_excitation"]
+    return ol
+
+
+def _world_wrappers():
+    x, f0 = torch.zeros(2400, dtype=torch.float64), torch.full((21,), 200.0, dtype=torch.float64)
+    t = np.arange(21) * 0.005
+    with _recorded() as ol:
+        world.cheaptrick(x, f0, t, 24000)
+        world.d4c_band_aperiodicity(x, f0, t, 24000)
+        world.sp2mc(torch.ones(21, 513, dtype=torch.float64), 39, 0.466)
+        world.convert_continuos_f0(f0)
+    assert _names(ol) == ["srn_world_cheaptrick", "srn_world_d4c", "srn_world_project", "srn_cont_f0"]
+    return ol
+
+
 PLANS = {
     "serenade B8xT1024 fp32": lambda: _inference(8, 1024, "fp32"),
     "serenade B8xT1024 bf16x3": lambda: _inference(8, 1024, "bf16x3"),
@@ -185,6 +281,12 @@ PLANS = {
     "transcriber 32000/23111": _transcriber,
     "stft log-mel 1024/256": lambda: features._Stft(CPU, 2, 24000, 1024, 256, 1024).ops,
     "stft loudness 2048/240 constant": lambda: features._Stft(CPU, 2, 24000, 2048, 240, 2048, "constant").ops,
+    "pyin 8000/5111": _pyin,
+    "harvest 24k 6000/4111": _harvest_24k,
+    "harvest 8k, no decimation": _harvest_8k,
+    "harvest two floors, item chunks": _harvest_two_floors,
+    "world analyzer 4800/3333 + excitation": _world_analyzer,
+    "world wrappers": _world_wrappers,
 }
 
 
@@ -203,7 +305,6 @@ def test_plan_ops_match_the_table(lib, name):
 def test_wave_batch_checks():
     """the input checks ContentVec.forward and TranscriptionModel.forward share, up to the upload (the lengths are
     checked after it)"""
-    import numpy as np
     for wave, kw in ((torch.zeros(2, 3, 8), {}), (torch.zeros(2, 2, 8), dict(allow_channel_dim=True)),
                      (np.zeros((1, 2, 1, 8)), dict(allow_channel_dim=True))):
         with pytest.raises(ValueError, match="^Model: "):
@@ -211,6 +312,16 @@ def test_wave_batch_checks():
     for wave, kw in ((np.zeros(8), {}), (torch.zeros(2, 1, 8), dict(allow_channel_dim=True))):
         with pytest.raises(RuntimeError, match="no CPU fallback"):  # rank and lengths pass; no device to upload to
             plan.wave_batch(wave, None, "cpu", "Model", **kw)
+
+
+def test_item_lengths():
+    assert plan.item_lengths(None, 3, 7, "Model") == (7, 7, 7)
+    for lengths in (torch.tensor([7, 1, 4]), [7, 1, 4], np.array([7, 1, 4]), (7.0, 1, 4)):
+        got = plan.item_lengths(lengths, 3, 7, "Model")
+        assert got == (7, 1, 4) and all(type(v) is int for v in got)
+    for bad in ([7, 1], [7, 1, 4, 4], [7, 0, 4], [7, 8, 4], torch.tensor([8, 1, 4]), np.array([0, 1, 4])):
+        with pytest.raises(ValueError, match="^Model: "):
+            plan.item_lengths(bad, 3, 7, "Model")
 
 
 if __name__ == "__main__":

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from serenade_amd import _shapes, sifigan, world  # noqa: E402
+from serenade_amd import _shapes, ops, sifigan, world  # noqa: E402
 from serenade_amd.utils.synth import fill_state_dict  # noqa: E402
 
 FS = 24000
@@ -76,7 +76,7 @@ def run(B=8, T=1024, dev=None, with_generator=True):
     out["frames_d4c_analysed"] = voiced
     # its kernels, separately
     x = torch.empty(wave.shape, dtype=torch.float64, device=dev)
-    world.check(world._lib.lib().srn_wave_to_f64(wave.data_ptr(), x.data_ptr(), wave.numel(), 1, world._stream()), "w")
+    ops.call("srn_wave_to_f64", wave, x, wave.numel(), 1)
     f0 = feats["f0"]
     t = torch.from_numpy(np.arange(F) * 5.0 / 1000.0).to(dev)[None].expand(B, F).contiguous()
     x_len, nf = world._i32([n] * B, dev), feats["nf"]
