@@ -73,6 +73,9 @@ __device__ __forceinline__ float srn_act(float v, int act, float slope) {
   }
 }
 
+// The wave helpers below are also inlined into pyin.hip and harvest.hip, which compile under
+// `#pragma clang fp contract(off)`; the pragma does not reach this header, and need not: none of them holds a
+// multiply followed by an add, so there is nothing to contract.
 // 64-lane wavefront all-reduce (sum) through cross-lane shuffles.
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -89,3 +92,14 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// LDS written by one lane of a wave becomes visible to the others: no s_barrier, the workgroup's other waves run on
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// p[0 .. n) = 0 on `stream` by a kernel (zero_u32_kernel, features.hip): a hipMemsetAsync node captured into a hipGraph
+// replays with a corrupted fill value from the second replay on on this ROCm stack (profiles/r3_graph_probe_*.json), so
+// nothing in this library issues one
+void srn_zero_u32(unsigned* p, int n, hipStream_t stream);

@@ -1,11 +1,27 @@
-// conv_common.h — pieces shared by the implicit-GEMM kernels (conv_gemm.hip, conv_halo.hip): fragment types,
-// the fp32 -> (hi, lo) bf16 split, the swizzled bf16 LDS image, the XCD-aware block map and the fused epilogue.
+// conv_common.h — pieces shared by the contraction kernels (the conv_*.hip families, resunit*.hip, tn_gemm.hip):
+// vector types, the fp32 -> (hi, lo) bf16 splits, the zero page, the buffer descriptor, the swizzled bf16
+// LDS image, the XCD-aware block map, the fused epilogue and the constants of the kernel choice.
 #pragma once
 #include "common.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// 256 B of zeros: the source of every padded / masked operand row.  One per translation unit (the library is built
+// without relocatable device code); internal linkage, so a file that never reads it emits nothing.
+static __device__ __attribute__((aligned(256), unused)) float g_zero_page[64];
+
+// The buffer descriptor of every raw_buffer_load / _store here: stride 0 and `bytes` as the number of records, so an
+// offset at or past `bytes` reads zeros and drops the store, which the kernels rely on instead of clamps.  Build it
+// from wave-uniform values only.  Which fields the bits of the flag word (the last argument) select: as measured
+// working, meaning not documented here.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t srn_buffer_rsrc(const float* base, const int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, bytes, 0x00020000);
+}
 
 // component-wise select (a float4 ?: is lowered through scratch memory by hipcc)
 __device__ __forceinline__ float4 sel4(unsigned ok, const float4& v) {
@@ -31,6 +47,17 @@ __device__ __forceinline__ void split4(const float4& v, bf16x4& hi, bf16x4& lo) 
   lo[1] = (__bf16)(v.y - (float)hi[1]);
   lo[2] = (__bf16)(v.z - (float)hi[2]);
   lo[3] = (__bf16)(v.w - (float)hi[3]);
+}
+
+// the same split on a pair: x = hi + lo, both round-to-nearest bf16; 5 VALU per pair
+__device__ __forceinline__ void split_pair(const float a, const float b, unsigned& hi, unsigned& lo) {
+  const f32x2 v = {a, b};
+  hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+  f32x2 hf;
+  hf.x = __builtin_bit_cast(float, hi << 16);
+  hf.y = __builtin_bit_cast(float, hi & 0xffff0000u);
+  const f32x2 l = v - hf;
+  lo = __builtin_bit_cast(unsigned, __builtin_convertvector(l, bf16x2));
 }
 
 // byte offset of bf16 element (row, k) in a [rows][32] bf16 tile with 64-B rows whose four 16-B chunks are
@@ -257,6 +284,7 @@ __device__ __forceinline__ void splitk_store(const SrnConvParams& p, f32x16 (&ac
 constexpr int SRN_NUM_CUS = 256;      // MI355X
 constexpr int SRN_HALO_MAX = 52;      // (k - 1) * dilation of the widest conv on the path (k 11, d 5 -> 50): the
                                       // receptive-field rows the halo and strip kernels stage beyond their tile
+constexpr int SRN_RESUNIT_HALO_MAX = 50;  // the same span as the fused residual unit stages it (resunit*.hip)
 constexpr int SRN_STRIP_BM = 128;     // conv_strip.hip: output rows per tile (4 waves x 32 rows)
 constexpr int SRN_MAX_KSPLIT = 8;     // conv_splitk.hip: most K slices of one launch
 

@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "conv_common.h"
+#include "fastdiv.h"
 #include "serenade_hip.h"
 
 namespace {
@@ -30,16 +31,6 @@ namespace {
 constexpr int BK = 32;
 constexpr int ROW = 36;  // floats per LDS row: 32 + 4 pad (144 B: conflict-free ds_read_b128 of 16 rows)
 constexpr unsigned OOB = 0x80000000u;  // >= every descriptor's num_records: the load returns zeros
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// n / d == (n * mul) >> shift for 0 <= n < 2^26 (host: make_fdiv); scalar operands stay on the scalar ALU
-struct FDiv {
-  uint32_t mul, shift;
-};
-__device__ __forceinline__ int fdiv(const int n, const FDiv d) {
-  return (int)(((uint64_t)(uint32_t)n * d.mul) >> d.shift);
-}
 
 struct F32Launch {
   int m_tiles, n_tiles, ksplit, per_slice, tiles_all;
@@ -83,15 +74,12 @@ __device__ __forceinline__ void f32_epilogue(const SrnConvParams& p, f32x16 (&ac
   const int ts = p.out_t_stride;
   const int rows_all = (p.T_out - 1) * ts + p.out_t_off;  // last output row that exists
   float* const out = p.out + (int64_t)zb * p.out_bs + (int64_t)zh * p.out_hs;
-  const __amdgpu_buffer_rsrc_t rs_o =
-      __builtin_amdgcn_make_buffer_rsrc(out, 0, (rows_all * p.ld_out + p.N_out) * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_o = srn_buffer_rsrc(out, (rows_all * p.ld_out + p.N_out) * 4);
   const bool has_res = p.res_mode != SRN_RES_NONE;
   const float* const res = has_res ? p.res + (int64_t)zb * p.res_bs + (int64_t)zh * p.res_hs : out;
   const float* const res2 = p.res2 ? p.res2 + (int64_t)zb * p.res2_bs : out;
-  const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(res), 0, has_res ? (rows_all * p.ld_res + p.N_out) * 4 : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_q = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(res2), 0, p.res2 ? (rows_all * p.ld_res2 + p.N_out) * 4 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_r = srn_buffer_rsrc(res, has_res ? (rows_all * p.ld_res + p.N_out) * 4 : 0);
+  const __amdgpu_buffer_rsrc_t rs_q = srn_buffer_rsrc(res2, p.res2 ? (rows_all * p.ld_res2 + p.N_out) * 4 : 0);
   const bool simple = !has_res && p.res2 == nullptr && p.post == SRN_POST_NONE;
   const float alpha = p.alpha;
   // per-lane byte offsets: row 4 lh of the sub-tile, column li
@@ -248,9 +236,9 @@ __global__ __launch_bounds__(256, C::MINW) void conv_f32_kernel(const SrnConvPar
   const int bytes0 = ((T_in - 1) * p.ld_in0 + p.C_in0) * 4;
   const int bytes1 = p.in1 ? ((T_in - 1) * p.ld_in1 + (p.C_in - p.C_in0)) * 4 : bytes0;
   const int bytesw = ((p.N - 1) * p.ldw + steps_all * BK) * 4;
-  const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a0), 0, bytes0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a1), 0, bytes1, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wb), 0, bytesw, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs0 = srn_buffer_rsrc(a0, bytes0);
+  const __amdgpu_buffer_rsrc_t rs1 = srn_buffer_rsrc(a1, bytes1);
+  const __amdgpu_buffer_rsrc_t rsw = srn_buffer_rsrc(wb, bytesw);
 
   // ---- per-lane row offsets
   const int c16 = (tid & 7) * 16;  // byte of this thread's 16-B piece inside the 128-B line
@@ -464,13 +452,6 @@ __global__ __launch_bounds__(256, C::MINW) void conv_f32_kernel(const SrnConvPar
 
   if (L.ksplit > 1) splitk_store<MT, NT>(p, acc, slice, z, t0, n0, wm0, wn0, lane);
   else f32_epilogue<MT, NT>(p, acc, zb, zh, t0, n0, wm0, wn0, lane);
-}
-
-FDiv make_fdiv(const uint32_t d) {
-  int lg = 0;
-  while ((1u << lg) < d) ++lg;
-  const int k = 26 + lg;
-  return FDiv{(uint32_t)(((1ull << k) + d - 1) / d), (uint32_t)k};
 }
 
 template <class C, int ACT>

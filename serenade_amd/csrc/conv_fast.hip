@@ -28,24 +28,7 @@ namespace {
 
 constexpr int BK = 32;
 
-// 256 B of zeros: the source of every padded / masked operand row
-__device__ __attribute__((aligned(256))) float g_zero_page[64];
-
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4m __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// x = hi + lo, both round-to-nearest bf16; 5 VALU per pair
-__device__ __forceinline__ void split_pair(const float a, const float b, unsigned& hi, unsigned& lo) {
-  const f32x2 v = {a, b};
-  hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-  f32x2 hf;
-  hf.x = __builtin_bit_cast(float, hi << 16);
-  hf.y = __builtin_bit_cast(float, hi & 0xffff0000u);
-  const f32x2 l = v - hf;
-  lo = __builtin_bit_cast(unsigned, __builtin_convertvector(l, bf16x2));
-}
 
 // x = hi + mid + lo EXACTLY (three round-to-nearest bf16 of successive exact residuals: 8 + 8 + 8 significand bits
 // cover fp32's 24; x - hi and (x - hi) - mid are exact in fp32)

@@ -19,21 +19,6 @@ constexpr int BM = SRN_STRIP_BM;  // output rows per tile: 4 waves x 32 rows
 constexpr int HALO_MAX = SRN_HALO_MAX;
 constexpr int HR_MAX = BM + HALO_MAX;
 
-__device__ __attribute__((aligned(256))) float g_zero_strip[64];
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void split_pair_s(const float a, const float b, unsigned& hi, unsigned& lo) {
-  const f32x2 v = {a, b};
-  hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-  f32x2 hf;
-  hf.x = __builtin_bit_cast(float, hi << 16);
-  hf.y = __builtin_bit_cast(float, hi & 0xffff0000u);
-  const f32x2 l = v - hf;
-  lo = __builtin_bit_cast(unsigned, __builtin_convertvector(l, bf16x2));
-}
-
 // CIN: input channels (32 / 64); NT: N / 32 (1 / 2); ACT: SRN_ACT_NONE / SRN_ACT_LEAKY.
 // LDS: W [tap][chunk][hi|lo][N rows][64 B swizzled] then A [chunk][hi|lo][HR_MAX rows][64 B swizzled].
 template <int CIN, int NT, int ACT>
@@ -86,7 +71,7 @@ __global__ __launch_bounds__(256, 2) void conv_strip_kernel(const SrnConvParams 
       const int f4 = q - row * F4R;
       const int ti = t0 + min_off + row;
       const bool ok = row < hr && ti >= 0 && ti < len_in;
-      const float* src = ok ? in0 + (int64_t)ti * p.ld_in0 + f4 * 4 : g_zero_strip + (f4 & 7) * 4;
+      const float* src = ok ? in0 + (int64_t)ti * p.ld_in0 + f4 * 4 : g_zero_page + (f4 & 7) * 4;
       pa[j] = *reinterpret_cast<const float4*>(src);
     }
   };
@@ -106,8 +91,8 @@ __global__ __launch_bounds__(256, 2) void conv_strip_kernel(const SrnConvParams 
           v.w = v.w > 0.f ? v.w : v.w * pro_slope;
         }
         uint2 hi, lo;
-        split_pair_s(v.x, v.y, hi.x, lo.x);
-        split_pair_s(v.z, v.w, hi.y, lo.y);
+        split_pair(v.x, v.y, hi.x, lo.x);
+        split_pair(v.z, v.w, hi.y, lo.y);
         const int chunk = f4 >> 3;
         const int off = bf_off(row, (f4 & 7) * 4);
         *reinterpret_cast<uint2*>(sA + (chunk * 2) * A_PLANE + off) = hi;

@@ -52,8 +52,7 @@ __global__ __launch_bounds__(128) void logmel_kernel(const float* __restrict__ s
   }
 }
 
-// zero-fill by a kernel: a hipMemsetAsync node captured into a hipGraph replays with a corrupted fill value from the
-// second replay on on this ROCm stack (profiles/r3_graph_probe_*.json), so nothing in this library issues one
+// the library's one zero-fill (common.h: srn_zero_u32 says why it is a kernel)
 __global__ void zero_u32_kernel(unsigned* __restrict__ p, const int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = 0u;
@@ -99,6 +98,10 @@ __global__ __launch_bounds__(256) void loudness_kernel(const float* __restrict__
 
 }  // namespace
 
+void srn_zero_u32(unsigned* p, const int n, hipStream_t stream) {
+  hipLaunchKernelGGL(zero_u32_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, p, n);
+}
+
 extern "C" int srn_pad_signal(const float* x, float* out, int B, int n, int pad, int ld, int mode, void* stream) {
   SRN_CHECK_ARG(x && out && B > 0 && n > 1 && pad >= 0 && ld >= n + 2 * pad && (mode == 0 || mode == 1),
                 "pad_signal: bad args");
@@ -126,7 +129,7 @@ extern "C" int srn_loudness(const float* spec, const float* a_weight_db, unsigne
   SRN_CHECK_ARG(spec && a_weight_db && gmax_ws && out && B > 0 && frames > 0 && n_bins > 0 && ld >= 2 * n_bins,
                 "loudness: bad args");
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(zero_u32_kernel, dim3((B + 255) / 256), dim3(256), 0, st, gmax_ws, B);
+  srn_zero_u32(gmax_ws, B, st);
   hipLaunchKernelGGL(power_max_kernel, dim3(frames < 512 ? frames : 512, B), dim3(256), 0, st, spec, gmax_ws, frames,
                      n_bins, ld);
   hipLaunchKernelGGL(loudness_kernel, dim3(frames, B), dim3(256), 0, st, spec, a_weight_db, gmax_ws, out, frames,

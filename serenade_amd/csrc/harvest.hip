@@ -41,18 +41,6 @@ constexpr int STEP4_GAP = 9;
 constexpr int SMOOTH_PAD = SRN_HARVEST_SMOOTH_PAD;
 constexpr int EXT_SLACK = EXTEND_FRAMES + 1;  // frames an extension can reach past a section's end
 
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __device__ __forceinline__ int64_t matlab_round(double x) { return x > 0.0 ? (int64_t)(x + 0.5) : (int64_t)(x - 0.5); }
 
 // ------------------------------------------------------------------------------------------------ decimation
@@ -127,7 +115,7 @@ __global__ __launch_bounds__(64) void harvest_decimate_kernel(const T* __restric
   wave_sync();
   double s = 0.0;
   for (int i = lane; i < ylen; i += 64) s += yb[i];
-  const double mean = wave_sum_f64(s) / (double)ylen;
+  const double mean = wave_sum_d(s) / (double)ylen;
   for (int i = lane; i < ylen; i += 64) yb[i] = yb[i] - mean;
 }
 
@@ -350,8 +338,8 @@ __global__ __launch_bounds__(NT) void harvest_refine_kernel(const double* __rest
           dc = dc + xd * cs;
           ds = ds + xd * sn;
         }
-        const double m_re = wave_sum_f64(mc), m_im = -wave_sum_f64(ms);
-        const double d_re = wave_sum_f64(dc), d_im = -wave_sum_f64(ds);
+        const double m_re = wave_sum_d(mc), m_im = -wave_sum_d(ms);
+        const double d_re = wave_sum_d(dc), d_im = -wave_sum_d(ds);
         const double numer = m_re * d_im - m_im * d_re;
         const double power = m_re * m_re + m_im * m_im;
         const double inst = power == 0.0 ? 0.0 : (double)bin * fs / (double)N + numer / power * fs / 2.0 / kPi;

@@ -22,12 +22,6 @@ constexpr int NT_OBS = 256;
 constexpr int NT_VIT = 1024;
 constexpr double kTiny = 2.2250738585072014e-308;  // np.finfo(np.float64).tiny
 
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 __device__ __forceinline__ int popc(unsigned long long m) { return __popcll(m); }
 
 // (value, index) maximum with the first index winning a tie

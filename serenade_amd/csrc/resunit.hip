@@ -28,23 +28,6 @@ int srn_resunit_f32_try(const SrnResUnitParams& p, hipStream_t stream);
 
 namespace {
 
-constexpr int RU_HALO_MAX = 50;  // (k - 1) * dilation of the widest unit on the path (k 11, d 5)
-
-__device__ __attribute__((aligned(256))) float g_zero_ru[64];
-
-typedef float f32x2r __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2r __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void split_pair_r(const float a, const float b, unsigned& hi, unsigned& lo) {
-  const f32x2r v = {a, b};
-  hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2r));
-  f32x2r hf;
-  hf.x = __builtin_bit_cast(float, hi << 16);
-  hf.y = __builtin_bit_cast(float, hi & 0xffff0000u);
-  const f32x2r l = v - hf;
-  lo = __builtin_bit_cast(unsigned, __builtin_convertvector(l, bf16x2r));
-}
-
 template <int C_, int PREC_, int NW_ = 4>
 struct RCfg {
   static constexpr int C = C_, PREC = PREC_, NW = NW_, NTH = 64 * NW_;
@@ -57,7 +40,7 @@ struct RCfg {
   static constexpr int BMI = 128 * MT;                 // intermediate rows per tile
   static constexpr int ROWB = PREC ? 64 : 144;         // bytes of one row of one 32-channel chunk (plane)
   static constexpr int PL = PREC ? 2 : 1;              // planes: (hi, lo) or fp32
-  static constexpr int A_ROWS = BMI + RU_HALO_MAX + 2;
+  static constexpr int A_ROWS = BMI + SRN_RESUNIT_HALO_MAX + 2;
   static constexpr int A_PLANE = A_ROWS * ROWB;
   static constexpr int A_BYTES = CH * PL * A_PLANE;
   static constexpr int UNIT = PL * C * ROWB;           // weights of one (tap, chunk): [plane][n][ROWB]
@@ -166,8 +149,8 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
         if (!((pa_ok >> j) & 1u)) v = make_float4(0.f, 0.f, 0.f, 0.f);
         if constexpr (BF) {
           uint2 hi, lo;
-          split_pair_r(v.x, v.y, hi.x, lo.x);
-          split_pair_r(v.z, v.w, hi.y, lo.y);
+          split_pair(v.x, v.y, hi.x, lo.x);
+          split_pair(v.z, v.w, hi.y, lo.y);
           *reinterpret_cast<uint2*>(sA + a_dst0 + j * RSTEP * 64) = hi;
           *reinterpret_cast<uint2*>(sA + a_dst0 + R::A_PLANE + j * RSTEP * 64) = lo;
         } else {
@@ -405,8 +388,8 @@ extern "C" int srn_hifigan_resunit(const SrnResUnitParams* pp, void* stream_) {
   SRN_CHECK_ARG(p.x && p.w1 && p.b1 && p.w2 && p.b2 && p.out, "resunit: null pointer");
   SRN_CHECK_ARG(p.n_batch > 0 && p.T > 0, "resunit: bad sizes");
   SRN_CHECK_ARG(p.C == 32 || p.C == 64, "resunit: C = %d (this fused kernel takes 32 or 64 channels)", p.C);
-  SRN_CHECK_ARG(p.k >= 1 && p.k % 2 == 1 && p.dilation >= 1 && (p.k - 1) * p.dilation <= RU_HALO_MAX,
-                "resunit: kernel %d / dilation %d outside the staged halo (%d rows)", p.k, p.dilation, RU_HALO_MAX);
+  SRN_CHECK_ARG(p.k >= 1 && p.k % 2 == 1 && p.dilation >= 1 && (p.k - 1) * p.dilation <= SRN_RESUNIT_HALO_MAX,
+                "resunit: kernel %d / dilation %d outside the staged halo (%d rows)", p.k, p.dilation, SRN_RESUNIT_HALO_MAX);
   SRN_CHECK_ARG(p.out != p.x && p.out != p.res2 - 0 ? true : p.out != p.x, "resunit: out must not alias x");
   SRN_CHECK_ARG(((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.w1) |
                   reinterpret_cast<uintptr_t>(p.w2)) & 15) == 0 && p.x_bs % 4 == 0,

@@ -18,27 +18,18 @@
 
 #include "common.h"
 #include "conv_common.h"
+#include "fastdiv.h"
 #include "serenade_hip.h"
 
 namespace {
 
-constexpr int HALO_MAX = 50;  // (k - 1) * dilation of the widest unit on the path (k 11, d 5): resunit.hip's RU_HALO_MAX
-constexpr int NTH = 512;      // eight waves: 32 x 32 of the tile per wave (resunit.hip, RCfg<C, 0, 8>)
-
-typedef unsigned u32x4r __attribute__((ext_vector_type(4)));
-
-struct FDivR {
-  uint32_t mul, shift;
-};
-__device__ __forceinline__ int fdivr(const int n, const FDivR d) {
-  return (int)(((uint64_t)(uint32_t)n * d.mul) >> d.shift);
-}
+constexpr int NTH = 512;  // eight waves: 32 x 32 of the tile per wave (resunit.hip, RCfg<C, 0, 8>)
 
 template <int C_>
 struct UCfg {
   static constexpr int C = C_, CH = C / 32;
   static constexpr int BMI = C == 32 ? 256 : 128;  // intermediate rows per tile (8 or 4 row groups of 32)
-  static constexpr int A_ROWS = BMI + HALO_MAX + 2;
+  static constexpr int A_ROWS = BMI + SRN_RESUNIT_HALO_MAX + 2;
   static constexpr int A_PLANE = A_ROWS * 144;     // one 32-channel chunk of the image: 144-B rows
   static constexpr int A_BYTES = CH * A_PLANE;
   static constexpr int UNIT = C * 144;             // weights of one (tap, chunk): [n][144 B]
@@ -52,7 +43,7 @@ struct UCfg {
 
 template <class R>
 __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitParams p, const int tiles_per_z,
-                                                             const int n_tiles, const FDivR d_tpz) {
+                                                             const int n_tiles, const FDiv d_tpz) {
   constexpr int C = R::C, CH = R::CH, BMI = R::BMI, G = R::G;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_u[];
   unsigned char* const sA = smem_u;
@@ -78,15 +69,15 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
   const int w_voff = w_n * (k * C * 4) + w_g * 128 + (tid & 7) * 16;
   const int w_dst = (w_g * C + w_n) * 144 + (tid & 7) * 16;
   const int w_bytes = C * k * C * 4;
-  const __amdgpu_buffer_rsrc_t rs_w1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w1), 0, w_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w2), 0, w_bytes, 0x00020000);
-  u32x4r wr;
+  const __amdgpu_buffer_rsrc_t rs_w1 = srn_buffer_rsrc(p.w1, w_bytes);
+  const __amdgpu_buffer_rsrc_t rs_w2 = srn_buffer_rsrc(p.w2, w_bytes);
+  u32x4 wr;
   auto w_load = [&](const int j) {  // a partial last stage reads on into the row (or past the tensor: zeros); never multiplied
     if (j >= S) wr = __builtin_amdgcn_raw_buffer_load_b128(rs_w2, w_voff, (j - S) * G * 128, 0);
     else wr = __builtin_amdgcn_raw_buffer_load_b128(rs_w1, w_voff, j * G * 128, 0);
   };
   auto w_store = [&](const int buf) {
-    *reinterpret_cast<u32x4r*>(sW + buf * R::STAGE + w_dst) = wr;
+    *reinterpret_cast<u32x4*>(sW + buf * R::STAGE + w_dst) = wr;
   };
 
   // ---- receptive-field image: piece j of this thread is float4 (tid % F4R) of image row tid / F4R + RSTEP j
@@ -95,12 +86,11 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
   const int a_r0 = tid / F4R;
   const int a_voff = (a_r0 * C + a_f4 * 4) * 4;
   const int a_dst0 = (a_f4 >> 3) * R::A_PLANE + a_r0 * 144 + (a_f4 & 7) * 16;
-  u32x4r pa[A_LD];
+  u32x4 pa[A_LD];
   auto load_a = [&](const int tile) {
-    const int z = fdivr(tile, d_tpz);
+    const int z = fdiv(tile, d_tpz);
     const int t0 = (tile - z * tiles_per_z) * BMo;
-    const __amdgpu_buffer_rsrc_t rs_x =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + (int64_t)z * p.x_bs), 0, T * C * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = srn_buffer_rsrc(p.x + (int64_t)z * p.x_bs, T * C * 4);
     const int v0 = a_voff + (t0 - p2 - p1) * (C * 4);  // negative rows wrap to offsets >= 2^31: out of range, zeros
 #pragma unroll
     for (int j = 0; j < A_LD; ++j) pa[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, v0 + j * (RSTEP * C * 4), 0, 0);
@@ -182,7 +172,7 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
   const int io_lane = ((wm0 + 4 * lh) * C + ng0 * 32 + li) * 4;          // x / res2 / out element of that row, tile-relative
 
   for (; tile < n_tiles; tile += gridDim.x) {
-    const int z = fdivr(tile, d_tpz);
+    const int z = fdiv(tile, d_tpz);
     const int t0 = (tile - z * tiles_per_z) * BMo;
     stage_a();  // the previous tile's conv2 ended on a barrier: nobody reads the image any more
     __syncthreads();
@@ -222,12 +212,10 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
     const int row_end = min(BMo, T - t0);
     const int64_t zoff = (int64_t)t0 * C;
     const int io_bytes = row_end * C * 4;  // the tile's rows that exist: anything past them is out of range
-    const __amdgpu_buffer_rsrc_t rs_xe = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.x + (int64_t)z * p.x_bs + zoff), 0, io_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_qe = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(has_q ? p.res2 + (int64_t)z * p.res2_bs + zoff : p.x), 0, has_q ? io_bytes : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_oe =
-        __builtin_amdgcn_make_buffer_rsrc(p.out + (int64_t)z * p.out_bs + zoff, 0, io_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_xe = srn_buffer_rsrc(p.x + (int64_t)z * p.x_bs + zoff, io_bytes);
+    const __amdgpu_buffer_rsrc_t rs_qe =
+        srn_buffer_rsrc(has_q ? p.res2 + (int64_t)z * p.res2_bs + zoff : p.x, has_q ? io_bytes : 0);
+    const __amdgpu_buffer_rsrc_t rs_oe = srn_buffer_rsrc(p.out + (int64_t)z * p.out_bs + zoff, io_bytes);
     if (wm0 + 32 <= row_end) {  // every row of this wave exists: row in the scalar offset
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
@@ -266,13 +254,6 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
   }
 }
 
-FDivR make_fdivr(const uint32_t d) {
-  int lg = 0;
-  while ((1u << lg) < d) ++lg;
-  const int k = 26 + lg;
-  return FDivR{(uint32_t)(((1ull << k) + d - 1) / d), (uint32_t)k};
-}
-
 template <class R>
 int launch_unit(const SrnResUnitParams& p, hipStream_t stream) {
   static SrnSmemAttr smem_attr;
@@ -283,7 +264,7 @@ int launch_unit(const SrnResUnitParams& p, hipStream_t stream) {
   if (n_tiles <= 0 || n_tiles >= (1ll << 26)) return 0;
   const int grid = (int)(n_tiles < 512 ? n_tiles : 512);  // persistent: two workgroups per CU
   hipLaunchKernelGGL((resunit_f32_kernel<R>), dim3(grid), dim3(NTH), R::SMEM, stream, p, tiles_per_z, (int)n_tiles,
-                     make_fdivr((uint32_t)tiles_per_z));
+                     make_fdiv((uint32_t)tiles_per_z));
   SRN_CHECK_LAUNCH();
   return 1;
 }

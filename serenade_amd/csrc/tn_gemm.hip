@@ -206,7 +206,6 @@ __global__ __launch_bounds__(256, 2) void tn_lean_kernel(const SrnTnGemmParams p
   constexpr int F4 = TB / 4;
   constexpr int ROWS_PER_PASS = 256 / F4;
   constexpr int NLD = BK / ROWS_PER_PASS;
-  typedef unsigned u32x4t __attribute__((ext_vector_type(4)));
   __shared__ __attribute__((aligned(16))) float lds[2][2][SLAB];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -242,14 +241,12 @@ __global__ __launch_bounds__(256, 2) void tn_lean_kernel(const SrnTnGemmParams p
     }
   };
   seat_b();
-  u32x4t ra[NLD], rb[NLD];
+  u32x4 ra[NLD], rb[NLD];
   auto load = [&]() {  // fetch the slab at (item, t0), then advance one slab
     const int it = min(item, p.n_items - 1);
     const int lend = p.len_b != nullptr ? min(p.T_b, p.len_b[zb * p.n_items + it]) : p.T_b;
-    const __amdgpu_buffer_rsrc_t rs_a =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A + (int64_t)it * p.a_is), 0, a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_b =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Bm + (int64_t)it * p.b_is), 0, lend * p.ldb * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a = srn_buffer_rsrc(A + (int64_t)it * p.a_is, a_bytes);
+    const __amdgpu_buffer_rsrc_t rs_b = srn_buffer_rsrc(Bm + (int64_t)it * p.b_is, lend * p.ldb * 4);
     const int soff_a = t0 * p.lda * 4;
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
@@ -269,8 +266,8 @@ __global__ __launch_bounds__(256, 2) void tn_lean_kernel(const SrnTnGemmParams p
   auto store = [&](const int st) {
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-      *reinterpret_cast<u32x4t*>(&lds[st][0][(lrow + ROWS_PER_PASS * i) * PITCH + lcol]) = ra[i];
-      *reinterpret_cast<u32x4t*>(&lds[st][1][(lrow + ROWS_PER_PASS * i) * PITCH + lcol]) = rb[i];
+      *reinterpret_cast<u32x4*>(&lds[st][0][(lrow + ROWS_PER_PASS * i) * PITCH + lcol]) = ra[i];
+      *reinterpret_cast<u32x4*>(&lds[st][1][(lrow + ROWS_PER_PASS * i) * PITCH + lcol]) = rb[i];
     }
   };
 

@@ -46,12 +46,6 @@ __device__ __forceinline__ float ord2f(unsigned u) {
   return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
-// zero-fill by a kernel: a hipMemsetAsync node captured into a hipGraph is not reliable on this stack (features.hip)
-__global__ void zero_u32_kernel(unsigned* __restrict__ p, const int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = 0u;
-}
-
 // one workgroup per (frame, item): the power spectrum of the frame into LDS, then mel bin m per thread (mel_t is
 // (nb, n_mels): lanes read consecutive addresses); dB of valid frames, 0 on frames at or past lens[b]; the item's
 // maximum dB goes to gmax[b] (order-preserving bits)
@@ -287,7 +281,7 @@ extern "C" int srn_mel_db(const float* spec, int ld_spec, int n_bins, const floa
                 "mel_db: bad sizes (B %d, T %d, n_bins %d, ld_spec %d, n_mels %d, ld_out %d)", B, T, n_bins, ld_spec,
                 n_mels, ld_out);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(zero_u32_kernel, dim3((B + 255) / 256), dim3(256), 0, st, gmax_ws, B);
+  srn_zero_u32(gmax_ws, B, st);
   SRN_CHECK_LAUNCH();
   hipLaunchKernelGGL(mel_db_kernel, dim3(T, B), dim3(256), (size_t)n_bins * sizeof(float), st, spec, ld_spec, n_bins,
                      mel_t, lens, gmax_ws, out, ld_out, T, n_mels, amin);
