@@ -94,12 +94,15 @@ typedef struct SrnConvParams {
   int32_t C_in0;     /* channels taken from in0; the remaining C_in - C_in0 come from in1 (multiple of 32 if < C_in) */
   int32_t C_w;       /* valid k per tap on the weight side (<= C_in; = C_in normally) */
   int32_t N;         /* GEMM N (weight rows) */
-  int32_t N_out;     /* stored output channels (N, or N/2 for GEGLU) */
+  int32_t N_out;     /* stored output channels: 0 (the default), N, or N/2 for GEGLU; anything else is refused */
   int32_t n_taps;
   int32_t tap_off[SRN_MAX_TAPS];
   int32_t in_stride;
   int32_t pad_reflect; /* 0: zero padding, 1: reflection at the tensor's ends, 2: reflection at 0 and at the item's own
-                        * end len_in[zb] (exact ragged batches: what nn.ReflectionPad1d does to the unpadded item) */
+                        * end len_in[zb] (exact ragged batches: what nn.ReflectionPad1d does to the unpadded item).
+                        * One mirror per end: t < 0 -> -t, then t >= end -> 2 (end - 1) - t; a row still outside
+                        * [0, len_in) after that reads as zero (tap offsets are only bounded by T_in, so an item
+                        * shorter than the table's reach gets zeros there, not a second reflection) */
   int32_t w_nmajor;    /* 0: w is [N][n_taps*C_in] (k contiguous); 1: w is [K][N] (n contiguous), n_taps == 1 */
   int32_t pro_act;
   float pro_slope;

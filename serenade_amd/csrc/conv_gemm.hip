@@ -746,6 +746,8 @@ int conv_params(const SrnConvParams* pp, SrnConvParams& p) {
   if (p.in_stride <= 0) p.in_stride = 1;
   if (p.out_t_stride <= 0) p.out_t_stride = 1;
   if (p.N_out <= 0) p.N_out = p.geglu ? p.N / 2 : p.N;
+  // the split-K reduce and the GroupNorm partial sums take the stored width from N: nothing narrower is a contract
+  SRN_CHECK_ARG(p.N_out == (p.geglu ? p.N / 2 : p.N), "conv_gemm: N_out (%d) must be 0, N, or N / 2 with GEGLU", p.N_out);
   if (p.geglu)
     SRN_CHECK_ARG(p.N % 64 == 0 && p.res_mode == SRN_RES_NONE && p.res2 == nullptr && p.post == SRN_POST_NONE,
                   "conv_gemm: GEGLU needs N %% 64 == 0 and no residual / post op");

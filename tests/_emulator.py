@@ -114,6 +114,8 @@ def emul_conv(kw):
                 val = torch.relu(val)
             elif g("post", 0) == _lib.POST_LEAKY:
                 val = F.leaky_relu(val, g("post_div", 1.0))
+            elif g("post", 0) == _lib.POST_GELU:
+                val = F.gelu(val)
             oidx = o_out + zb * g("out_bs", 0) + zh * g("out_hs", 0) + (t * ots + oto).unsqueeze(1) * g("ld_out") + cols
             if g("out_tr") is not None:  # transposed tail: columns >= col0 go to out_tr[zb][c - col0][t] instead
                 c0 = g("out_tr_col0", 0)
