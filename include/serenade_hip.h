@@ -702,6 +702,38 @@ int srn_harvest_contour(const double* refined, const double* score, const int32_
                         int64_t out_stride, int B, int F1, int n_cand, int F_out, int voice_range_minimum,
                         double frame_period, void* stream);
 
+/*
+ * The waveform arithmetic between the file on disk and the feature front-ends (serenade_amd/audio.py drives it,
+ * tests/_audio_ref.py is the restatement): resampling, silence trimming and the reflect tail pad of
+ * serenade/bin/preprocess.py:405-432 and the resampling of ssc_postprocessing.py:146.  All three are ragged: x (B, N)
+ * float32 (x_is_f64 0) or float64 (1) at row stride x_bs, item b has its own sample count and nothing past it is read;
+ * every sum is fp64 in an order that depends on the item alone, so each item gets bit for bit what its B = 1 call
+ * gets; y has x's dtype (the fp64 result rounded once for float32).
+ */
+#define SRN_RESAMPLE_TILE 256      /* outputs per workgroup */
+#define SRN_RESAMPLE_MAX_SPAN 8192 /* inputs one tile may touch (64 KiB of LDS): ceil(255 M / L) + K */
+/* preprocess.py:405-412, :428-432 and ssc_postprocessing.py:146 -> librosa.resample as a polyphase Kaiser-windowed
+ * sinc (the filter is specified in audio.py / DESIGN.md 7e; soxr itself is not restated).  L = target / g,
+ * M = orig / g: y[b][m] = sum_j x[b][j] h[m M - j L] over 0 <= j < lens[b], j ascending, for m < out_lens[b]
+ * (<= n_out_max), zeros up to n_out_max.  table (K, L) float64, tap-major: table[k][p] = h[p - (k - q_lo) L], 0 where
+ * the argument lies beyond the filter's half length; output m uses phase p = m M mod L on the inputs
+ * floor(m M / L) - q_lo + k, k = 0 .. K - 1. */
+int srn_resample(const void* x, int x_is_f64, int64_t x_bs, const int32_t* lens, const int32_t* out_lens,
+                 const double* table, void* y, int64_t y_bs, int B, int N, int n_out_max, int L, int M, int K,
+                 int q_lo, void* stream);
+/* preprocess.py:416-422 -> the frame decisions of librosa.effects.trim.  Item b has 1 + lens[b] / hop frames (at most
+ * T_max), frame t the samples [t hop - frame_length / 2, + frame_length) with zeros outside the item; ms (B, T_max)
+ * float64 scratch receives the mean of squares of each.  Frame t is non-silent iff
+ * max(1e-10, ms_t) > factor max(1e-10, max_t ms_t), factor = 10^(-top_db / 10).  bounds (B, 2) int32:
+ * (first hop, min(lens[b], (last + 1) hop)) over the non-silent frames, (0, 0) when there is none. */
+int srn_trim_bounds(const void* x, int x_is_f64, int64_t x_bs, const int32_t* lens, double* ms, int32_t* bounds, int B,
+                    int N, int T_max, int frame_length, int hop, double factor, void* stream);
+/* preprocess.py:416-426 -> the trimmed slice and np.pad(audio, (0, pad), mode="reflect") in one pass:
+ * y[b][i] = x[b][starts[b] + i] for i < counts[b], x[b][starts[b] + counts[b] - 2 - (i - counts[b])] for the next pad
+ * samples (pad < counts[b]: one reflection), zeros up to width.  starts[b] + counts[b] must lie within the item. */
+int srn_wave_window(const void* x, int x_is_f64, int64_t x_bs, const int32_t* starts, const int32_t* counts, int pad,
+                    void* y, int64_t y_bs, int B, int width, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,6 +193,9 @@ _SIGS = {
     "srn_harvest_candidates": (c_int, [_P] * 4 + [c_int] * 4 + [_P]),
     "srn_harvest_refine": (c_int, [_P, c_int64] + [_P] * 5 + [c_int] * 3 + [c_double] * 3 + [_P]),
     "srn_harvest_contour": (c_int, [_P] * 9 + [c_int64, _P, c_int, _P, _P, c_int64] + [c_int] * 5 + [c_double, _P]),
+    "srn_resample": (c_int, [_P, c_int, c_int64, _P, _P, _P, _P, c_int64] + [c_int] * 7 + [_P]),
+    "srn_trim_bounds": (c_int, [_P, c_int, c_int64, _P, _P, _P] + [c_int] * 5 + [c_double, _P]),
+    "srn_wave_window": (c_int, [_P, c_int, c_int64, _P, _P, c_int, _P, c_int64, c_int, c_int, _P]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -12,9 +12,11 @@ unavailable), the waveform is re-analysed (serenade_amd.world.Analyzer: CheapTri
 aperiodicity, continuous F0, dilated factors, sine excitation) and `NAME_sifigan.wav` (PCM_16) is written next to it.
 Files without an F0 contour or without a voiced frame are skipped, as in the reference.
 
-Not reproduced: `pw.harvest` (:147-153) -- its F0 track is discarded by the reference, only its frame count and time
-axis are used, and those are closed-form; `librosa.resample` for inputs at another rate (the decode CLI writes at
-`sample_rate`): such files raise.  Under torchrun the file list is split over the ranks (no collective)."""
+A wav at another rate than `sample_rate` is resampled on the GPU as the reference does with librosa (:146), in float64
+on the samples as read (`load_wave`, serenade_amd.audio.resample: DESIGN.md 7e states how far that filter and soxr's
+agree).  Not reproduced: `pw.harvest` (:147-153) -- its F0 track is discarded by the reference, only its frame count
+and time axis are used, and those are closed-form.  Under torchrun the file list is split over the ranks (no
+collective)."""
 import copy
 import glob
 import logging
@@ -26,7 +28,7 @@ import numpy as np
 import torch
 import yaml
 
-from serenade_amd import parallel, sifigan, world
+from serenade_amd import audio, parallel, sifigan, world
 from serenade_amd.utils.io import read_feats, read_wav, write_wav_pcm16
 
 logger = logging.getLogger(__name__)
@@ -61,6 +63,18 @@ def parse_overrides(argv):
             raise SystemExit(f"unknown option {key!r}")
         node[leaf] = yaml.safe_load(text) if text != "" else None
     return cfg
+
+
+def load_wave(path, sample_rate, device):
+    """ssc_postprocessing.py:144-146: the mono wav at `path` as a (1, n) float32 tensor on `device` at `sample_rate`;
+    a file at another rate goes through audio.resample in float64, as librosa.resample gets sf.read's output"""
+    x, sr = read_wav(path)
+    if np.ndim(x) != 1:
+        raise ValueError(f"{path}: {np.shape(x)[1]} channels; the analysis expects mono audio")
+    if sr != sample_rate:
+        x = audio.resample(torch.from_numpy(np.asarray(x, dtype=np.float64)).to(device), sr, sample_rate)
+        return x.to(torch.float32).view(1, -1)
+    return torch.from_numpy(np.asarray(x, dtype=np.float32)).to(device).view(1, -1)
 
 
 class PostJob:
@@ -102,16 +116,11 @@ class PostJob:
         return None
 
     def process(self, wav_file):
-        x, sr = read_wav(wav_file)
-        if np.ndim(x) != 1:
-            raise ValueError(f"{wav_file}: {np.shape(x)[1]} channels; the analysis expects mono audio")
-        if sr != self.cfg["sample_rate"]:
-            raise NotImplementedError(f"{wav_file}: {sr} Hz, expected {self.cfg['sample_rate']} (no resampler built)")
         f0 = self.f0_of(wav_file)
         if f0 is None:
             print(f"No h5 file containing f0 found for {wav_file}")
             return 0
-        wave = torch.from_numpy(np.asarray(x, dtype=np.float32)).to(self.device).view(1, -1)
+        wave = load_wave(wav_file, self.cfg["sample_rate"], self.device)
         in_signal, c, dfs, feats = self.analyzer(wave, [wave.size(1)], [np.asarray(f0)])
         if int(feats["ok"][0]) == 0:
             logger.warning(f"{wav_file}: all of the f0 values are 0.")
