@@ -152,6 +152,12 @@ int64_t srn_conv_gemm_workspace_bytes(const SrnConvParams* p);
 /* the kernel srn_conv_gemm would launch for *p, without touching a device: out = {SRN_FAMILY_*, tile id, K slices}
  * (K slices > 1: the f32 / fast slice launch followed by the split-K reduce).  Validates *p as srn_conv_gemm does. */
 int srn_conv_gemm_route(const SrnConvParams* p, int32_t out[3]);
+/* the kernel forms behind srn_conv_gemm, from the lists the launch and the route read, without touching a device.
+ * Returns their number and fills the first `capacity` rows of SRN_FORM_FIELDS values each (rows may be NULL):
+ * {SRN_FAMILY_*, tile id, SRN_PREC_* of the arithmetic, B is n-major, the family's form for K slices,
+ *  tile rows, tile columns, columns of one wave's tile, LDS stages}.  The generic family's fp32 rows run bf16x6 too. */
+#define SRN_FORM_FIELDS 9
+int srn_conv_gemm_forms(int32_t* rows, int capacity);
 
 /*
  * GroupNorm(8 groups, eps) -> Mish -> (+ time_bias[c]) -> * mask   (Block1D tail + the time-embedding add of

@@ -3,6 +3,7 @@
 There is no fallback: if the library cannot be loaded the product path raises.  The CPU
 oracle under ``oracle/`` is never imported from here.
 """
+import collections
 import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
@@ -114,6 +115,7 @@ _SIGS = {
     "srn_conv_gemm": (c_int, [POINTER(SrnConvParams), _P]),
     "srn_conv_gemm_workspace_bytes": (c_int64, [POINTER(SrnConvParams)]),
     "srn_conv_gemm_route": (c_int, [POINTER(SrnConvParams), POINTER(c_int32)]),
+    "srn_conv_gemm_forms": (c_int, [POINTER(c_int32), c_int]),
     "srn_hifigan_resunit": (c_int, [POINTER(SrnResUnitParams), _P]),
     "srn_gn_mish_apply": (c_int, [_P, _P, _P, _P, _P, c_int64, _P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
     "srn_resblock_tail": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int,
@@ -226,3 +228,16 @@ def check(rc, what=""):
     if rc != 0:
         msg = lib().srn_last_error().decode("utf-8", "replace")
         raise RuntimeError(f"libserenade_hip {what} failed (rc={rc}): {msg}")
+
+
+# one row of srn_conv_gemm_forms (SRN_FORM_FIELDS values): a kernel form behind srn_conv_gemm
+ConvForm = collections.namedtuple("ConvForm", "family tile precision nmajor kslices bm bn wn stages")
+
+
+def conv_forms():
+    """the kernel forms the library's launch and route read, in the library's order"""
+    k = len(ConvForm._fields)
+    n = lib().srn_conv_gemm_forms(None, 0)
+    rows = (c_int32 * (n * k))()
+    assert lib().srn_conv_gemm_forms(rows, n) == n
+    return [ConvForm(*rows[i * k:(i + 1) * k]) for i in range(n)]

@@ -36,6 +36,17 @@ __device__ __forceinline__ float4 leaky4(float4 v, float slope) {
   return v;
 }
 
+// run-time prologue activation (SiLU / Mish; act(0) == 0 for every supported activation)
+__device__ __forceinline__ float4 act4(float4 v, int act, float slope) {
+  if (act != SRN_ACT_NONE) {
+    v.x = srn_act(v.x, act, slope);
+    v.y = srn_act(v.y, act, slope);
+    v.z = srn_act(v.z, act, slope);
+    v.w = srn_act(v.w, act, slope);
+  }
+  return v;
+}
+
 // fp32 -> (hi, lo) bf16 pair with x ~= hi + lo to 2^-17 relative (round-to-nearest twice; hipcc emits
 // v_cvt_pk_bf16_f32 + shift/and + v_sub: 3 VALU ops per element)
 __device__ __forceinline__ void split4(const float4& v, bf16x4& hi, bf16x4& lo) {
@@ -311,14 +322,75 @@ inline int srn_strip_lds_bytes(const SrnConvParams& p) {
   return p.n_taps * p.C_in * p.N * 4 + (p.C_in / 32) * 2 * (SRN_STRIP_BM + SRN_HALO_MAX) * 64;
 }
 
-// The launchers of the kernel families behind srn_conv_gemm.  Each launches what it is told: `p` has been validated
-// and defaulted by srn_conv_gemm and routed by conv_route (conv_gemm.hip), which holds every eligibility rule.
-// `tile` is an id of conv_gemm.hip's tile table; `ksplit` > 1 (f32 / fast only) stores the partial sums of K slices
-// to p.ws for srn_splitk_reduce.  Return 0, or < 0 on error.
-int srn_conv_f32_launch(const SrnConvParams& p, int tile, int ksplit, hipStream_t stream);    // conv_f32.hip
-int srn_conv_fast_launch(const SrnConvParams& p, int tile, int ksplit, hipStream_t stream);   // conv_fast.hip
-int srn_conv_halo_launch(const SrnConvParams& p, int tile, int ksplit, hipStream_t stream);   // conv_halo.hip
-int srn_conv_strip_launch(const SrnConvParams& p, int tile, int ksplit, hipStream_t stream);  // conv_strip.hip
+// ---------------------------------------------------------------------------------------------------------------------
+// The kernel forms behind srn_conv_gemm.  What a tile id means is stated here, once; which forms exist is stated by
+// each family's list in its own file.  conv_gemm.hip's conv_route, the launch and srn_conv_gemm_forms read those lists.
+
+// tile id -> output tile of a workgroup (bm x bn) and of one of its four waves (wm x wn).  Id 0 is conv_strip.hip's
+// kernel (four waves x 32 rows, one column tile of at most 64); ids 6 and 8 have no kernel (conv_gemm.hip's kTiles).
+struct SrnTileGeom {
+  int bm, bn, wm, wn;
+};
+constexpr SrnTileGeom kSrnTileGeom[] = {
+    /* 0 */ {SRN_STRIP_BM, 64, 32, 32}, /* 1 */ {128, 128, 64, 64}, /* 2 */ {128, 64, 32, 64}, /* 3 */ {64, 128, 32, 64},
+    /* 4 */ {64, 64, 32, 32},           /* 5 */ {128, 32, 32, 32},  /* 6 */ {128, 128, 64, 64}, /* 7 */ {64, 64, 32, 32},
+    /* 8 */ {128, 64, 32, 64},          /* 9 */ {64, 128, 32, 64},  /* 10 */ {32, 64, 32, 32},  /* 11 */ {64, 64, 32, 32},
+};
+constexpr int SRN_TILE_IDS = sizeof(kSrnTileGeom) / sizeof(kSrnTileGeom[0]);
+// the first four arguments of a family's config template for tile id ID
+#define SRN_TILE(ID) kSrnTileGeom[ID].bm, kSrnTileGeom[ID].bn, kSrnTileGeom[ID].wm, kSrnTileGeom[ID].wn
+
+// One kernel form: `launch` runs `p` (validated and defaulted by srn_conv_gemm, routed by conv_route, which holds every
+// eligibility rule) on the kernel of this tile id, arithmetic and B layout; ksplit > 1 (rows with `kslices` only)
+// stores the partial sums of K slices to p.ws for srn_splitk_reduce.  Returns 0, or < 0 on error.
+typedef int (*SrnFormLaunch)(const SrnConvParams& p, int ksplit, hipStream_t stream);
+struct SrnConvForm {
+  int tile, precision;  // id of kSrnTileGeom, SRN_PREC_* of the arithmetic
+  bool nmajor;          // B is [k][n] (p.w_nmajor)
+  int stages;           // LDS stages of the main loop
+  bool kslices;         // the family's form for K slices
+  SrnFormLaunch launch;
+};
+struct SrnFormList {
+  const SrnConvForm* rows;
+  int n;
+  template <int N>
+  constexpr SrnFormList(const SrnConvForm (&r)[N]) : rows(r), n(N) {}
+};
+
+// a row of a family's list for the config C it launches (built with SRN_TILE(ID)): C's tiles must be what the id says
+template <int ID, class C>
+constexpr SrnConvForm srn_form(int precision, bool nmajor, int stages, bool kslices, SrnFormLaunch launch) {
+  static_assert(C::BM == kSrnTileGeom[ID].bm && C::BN == kSrnTileGeom[ID].bn && C::WM == kSrnTileGeom[ID].wm &&
+                    C::WN == kSrnTileGeom[ID].wn, "the config's tiles differ from the id's row of kSrnTileGeom");
+  return {ID, precision, nmajor, stages, kslices, launch};
+}
+
+// each family's list, from its own file
+SrnFormList srn_conv_generic_forms();  // conv_gemm.hip
+SrnFormList srn_conv_f32_forms();      // conv_f32.hip
+SrnFormList srn_conv_fast_forms();     // conv_fast.hip
+SrnFormList srn_conv_halo_forms();     // conv_halo.hip
+SrnFormList srn_conv_strip_forms();    // conv_strip.hip
+
+// What every tiled launcher does first: the kernel's LDS granted on this device, the tile grid, its size checked.
+// `attr` is the launcher's function-local static (one per kernel instantiation).
+struct SrnTileGrid {
+  int m_tiles, n_tiles;
+  int64_t tiles, blocks;  // tiles of the launch; workgroups = tiles x K slices
+};
+template <class C, class K>
+int srn_tile_grid(const char* who, SrnSmemAttr& attr, K* kernel, int smem, const SrnConvParams& p, int ksplit,
+                  int64_t limit, SrnTileGrid& g) {
+  if (const int e = attr.ensure(reinterpret_cast<const void*>(kernel), smem)) return e;
+  g.m_tiles = (p.T_out + C::BM - 1) / C::BM;
+  g.n_tiles = (p.N + C::BN - 1) / C::BN;
+  g.tiles = (int64_t)p.n_batch * p.n_head * g.m_tiles * g.n_tiles;
+  g.blocks = g.tiles * ksplit;
+  SRN_CHECK_ARG(g.blocks > 0 && g.blocks < limit, "%s: bad grid %lld", who, (long long)g.blocks);
+  return 0;
+}
+
 // implemented in conv_splitk.hip: the workspace K slices need, and the reduction + epilogue over the partial sums
 int64_t srn_splitk_bytes(const SrnConvParams& p, int ksplit);
 int srn_splitk_reduce(const SrnConvParams& p, int ksplit, hipStream_t stream);

@@ -457,49 +457,45 @@ __global__ __launch_bounds__(256, C::MINW) void conv_f32_kernel(const SrnConvPar
 template <class C, int ACT>
 int launch_f32_2(const SrnConvParams& p, hipStream_t stream, const int ksplit) {
   static SrnSmemAttr smem_attr;
-  if (const int e = smem_attr.ensure(reinterpret_cast<const void*>(&conv_f32_kernel<C, ACT>), C::SMEM_BYTES)) return e;
+  SrnTileGrid g;  // the magic divisions hold below 2^26 workgroups
+  if (const int e = srn_tile_grid<C>("conv_f32", smem_attr, &conv_f32_kernel<C, ACT>, C::SMEM_BYTES, p, ksplit, 1ll << 26, g))
+    return e;
   F32Launch L;
-  L.m_tiles = (p.T_out + C::BM - 1) / C::BM;
-  L.n_tiles = (p.N + C::BN - 1) / C::BN;
+  L.m_tiles = g.m_tiles;
+  L.n_tiles = g.n_tiles;
   L.ksplit = ksplit;
   const int cpt = p.C_in / BK;
   const int steps_all = p.n_taps * cpt;
   L.per_slice = (steps_all + ksplit - 1) / ksplit;
-  const int64_t tiles_all = (int64_t)p.n_batch * p.n_head * L.m_tiles * L.n_tiles;
-  const int64_t blocks = tiles_all * ksplit;
-  SRN_CHECK_ARG(blocks > 0 && blocks < (1ll << 26), "conv_f32: %lld workgroups (the magic divisions hold below 2^26)",
-                (long long)blocks);
-  L.tiles_all = (int)tiles_all;
+  L.tiles_all = (int)g.tiles;
   L.d_per_z = make_fdiv((uint32_t)(L.m_tiles * L.n_tiles));
   L.d_band = make_fdiv((uint32_t)(TILE_BAND * L.n_tiles));
   L.d_head = make_fdiv((uint32_t)p.n_head);
-  L.d_tiles_all = make_fdiv((uint32_t)tiles_all);
+  L.d_tiles_all = make_fdiv((uint32_t)g.tiles);
   L.d_cpt = make_fdiv((uint32_t)cpt);
-  hipLaunchKernelGGL((conv_f32_kernel<C, ACT>), dim3((unsigned)blocks), dim3(256), C::SMEM_BYTES, stream, p, L);
+  hipLaunchKernelGGL((conv_f32_kernel<C, ACT>), dim3((unsigned)g.blocks), dim3(256), C::SMEM_BYTES, stream, p, L);
   SRN_CHECK_LAUNCH();
   return 0;
 }
 
 template <class C>
-int launch_f32(const SrnConvParams& p, hipStream_t stream, const int ksplit) {
+int launch_f32(const SrnConvParams& p, const int ksplit, hipStream_t stream) {
   if (p.pro_act == SRN_ACT_NONE) return launch_f32_2<C, SRN_ACT_NONE>(p, stream, ksplit);
   return launch_f32_2<C, SRN_ACT_LEAKY>(p, stream, ksplit);
 }
 
+// Tile ids: 5 = 128 x 32 (thin outputs, N = 32), 7 = 64 x 64, 9 = 64 x 128 (conv_fast.hip's single-stage ids, same
+// results bit for bit), 10 = 32 x 64 with the step split over two wave pairs, 11 = 64 x 64 with two register sets (loads
+// two steps ahead: small grids and split-K slices, where a workgroup is alone on its CU).  All stage once.
+template <int ID, int KW, int MINW, int PF = 1>
+constexpr SrnConvForm f32_form(bool kslices = false) {
+  using C = TCfg<SRN_TILE(ID), KW, MINW, PF>;
+  return srn_form<ID, C>(SRN_PREC_FP32, false, 1, kslices, launch_f32<C>);
+}
+constexpr SrnConvForm kF32Forms[] = {
+    f32_form<5, 1, 6>(), f32_form<7, 1, 6>(), f32_form<9, 1, 4>(), f32_form<10, 2, 6>(), f32_form<11, 1, 5, 2>(true),
+};
+
 }  // namespace
 
-// Tile ids: 5 = 128 x 32, 7 = 64 x 64, 9 = 64 x 128 (conv_fast.hip's single-stage ids, same results bit for bit), 10 =
-// 32 x 64 with the step split over two wave pairs, 11 = 64 x 64 with two register sets (loads two steps ahead: small
-// grids and split-K slices, where a workgroup is alone on its CU).
-int srn_conv_f32_launch(const SrnConvParams& p, int tile, int ksplit, hipStream_t stream) {
-  switch (tile) {
-    case 5: return launch_f32<TCfg<128, 32, 32, 32, 1, 6>>(p, stream, ksplit);  // thin outputs (N = 32)
-    case 7: return launch_f32<TCfg<64, 64, 32, 32, 1, 6>>(p, stream, ksplit);
-    case 9: return launch_f32<TCfg<64, 128, 32, 64, 1, 4>>(p, stream, ksplit);
-    case 10: return launch_f32<TCfg<32, 64, 32, 32, 2, 6>>(p, stream, ksplit);
-    case 11: return launch_f32<TCfg<64, 64, 32, 32, 1, 5, 2>>(p, stream, ksplit);
-    default: break;
-  }
-  srn_set_error("conv_f32: no tile id %d", tile);
-  return -1;
-}
+SrnFormList srn_conv_f32_forms() { return kF32Forms; }

@@ -250,10 +250,7 @@ __global__ __launch_bounds__(256, C::MIN_BLOCKS) void conv_fast_kernel(const Srn
       for (int i = 0; i < C::A_LD; ++i) {
         float4 v = R.pa[i];
         if constexpr (ACT == SRN_ACT_LEAKY) {
-          v.x = v.x > 0.f ? v.x : v.x * pro_slope;
-          v.y = v.y > 0.f ? v.y : v.y * pro_slope;
-          v.z = v.z > 0.f ? v.z : v.z * pro_slope;
-          v.w = v.w > 0.f ? v.w : v.w * pro_slope;
+          v = leaky4(v, pro_slope);
         } else if constexpr (ACT < 0) {
           v.x = srn_act(v.x, pro_act, pro_slope);
           v.y = srn_act(v.y, pro_act, pro_slope);
@@ -276,10 +273,7 @@ __global__ __launch_bounds__(256, C::MIN_BLOCKS) void conv_fast_kernel(const Srn
     for (int i = 0; i < C::A_LD; ++i) {
       float4 v = R.pa[i];
       if constexpr (ACT == SRN_ACT_LEAKY) {
-        v.x = v.x > 0.f ? v.x : v.x * pro_slope;
-        v.y = v.y > 0.f ? v.y : v.y * pro_slope;
-        v.z = v.z > 0.f ? v.z : v.z * pro_slope;
-        v.w = v.w > 0.f ? v.w : v.w * pro_slope;
+        v = leaky4(v, pro_slope);
       } else if constexpr (ACT < 0) {
         v.x = srn_act(v.x, pro_act, pro_slope);
         v.y = srn_act(v.y, pro_act, pro_slope);
@@ -559,74 +553,47 @@ template <class C, int ACT, bool WPL>
 int launch_fast3(const SrnConvParams& p, hipStream_t stream, const int ksplit) {
   constexpr int SMEM = C::SMEM_BYTES;
   static SrnSmemAttr smem_attr;
-  if (const int e = smem_attr.ensure(reinterpret_cast<const void*>(&conv_fast_kernel<C, ACT, WPL>), SMEM)) return e;
-  const int m_tiles = (p.T_out + C::BM - 1) / C::BM;
-  const int n_tiles = (p.N + C::BN - 1) / C::BN;
-  const int64_t blocks = (int64_t)p.n_batch * p.n_head * m_tiles * n_tiles * ksplit;
-  SRN_CHECK_ARG(blocks > 0 && blocks < (1ll << 31), "conv_fast: bad grid %lld", (long long)blocks);
-  hipLaunchKernelGGL((conv_fast_kernel<C, ACT, WPL>), dim3((unsigned)blocks), dim3(256), SMEM, stream, p, m_tiles,
-                     n_tiles, ksplit);
+  SrnTileGrid g;
+  if (const int e = srn_tile_grid<C>("conv_fast", smem_attr, &conv_fast_kernel<C, ACT, WPL>, SMEM, p, ksplit, 1ll << 31, g))
+    return e;
+  hipLaunchKernelGGL((conv_fast_kernel<C, ACT, WPL>), dim3((unsigned)g.blocks), dim3(256), SMEM, stream, p, g.m_tiles,
+                     g.n_tiles, ksplit);
   SRN_CHECK_LAUNCH();
   return 0;
 }
 
 template <class C, int ACT>
-int launch_fast2(const SrnConvParams& p, bool wpl, hipStream_t stream, int ks) {
+int launch_fast2(const SrnConvParams& p, hipStream_t stream, int ks) {
   if constexpr (C::PREC == 0) return launch_fast3<C, ACT, false>(p, stream, ks);  // fp32: plain weight rows
-  else return wpl ? launch_fast3<C, ACT, true>(p, stream, ks) : launch_fast3<C, ACT, false>(p, stream, ks);
+  else return srn_weight_planes(p) ? launch_fast3<C, ACT, true>(p, stream, ks) : launch_fast3<C, ACT, false>(p, stream, ks);
 }
 
 template <class C>
-int launch_fast(const SrnConvParams& p, bool wpl, hipStream_t stream, int ks = 1) {
-  if (p.pro_act == SRN_ACT_NONE) return launch_fast2<C, SRN_ACT_NONE>(p, wpl, stream, ks);
-  if (p.pro_act == SRN_ACT_LEAKY) return launch_fast2<C, SRN_ACT_LEAKY>(p, wpl, stream, ks);
-  return launch_fast2<C, -1>(p, wpl, stream, ks);
+int launch_fast(const SrnConvParams& p, int ks, hipStream_t stream) {
+  if (p.pro_act == SRN_ACT_NONE) return launch_fast2<C, SRN_ACT_NONE>(p, stream, ks);
+  if (p.pro_act == SRN_ACT_LEAKY) return launch_fast2<C, SRN_ACT_LEAKY>(p, stream, ks);
+  return launch_fast2<C, -1>(p, stream, ks);
 }
+
+// K slices always take the 64 x 64 tile (they exist because the grid is small).  Ids 7 and 9: one LDS stage.  bf16x6
+// id 1 has one stage too (48 KB, three workgroups per CU): its two-stage form (96 KB, one per CU) measured 0-40 % slower.
+template <int ID, int NSTAGE, int PREC>
+constexpr SrnConvForm fast_form(bool kslices = false) {
+  using C = FCfg<SRN_TILE(ID), NSTAGE, PREC>;
+  return srn_form<ID, C>(PREC == 0 ? SRN_PREC_FP32 : PREC == 2 ? SRN_PREC_BF16X6 : SRN_PREC_BF16X3, false, NSTAGE,
+                         kslices, launch_fast<C>);
+}
+constexpr SrnConvForm kFastForms[] = {
+    // <id, LDS stages, PREC>: exact fp32, split-bf16, bf16x6
+    fast_form<1, 2, 0>(),     fast_form<1, 2, 1>(),     fast_form<1, 1, 2>(),
+    fast_form<2, 2, 0>(),     fast_form<2, 2, 1>(),     fast_form<2, 2, 2>(),
+    fast_form<3, 2, 0>(),     fast_form<3, 2, 1>(),     fast_form<3, 2, 2>(),
+    fast_form<4, 2, 0>(true), fast_form<4, 2, 1>(true), fast_form<4, 2, 2>(true),
+    fast_form<5, 2, 0>(),     fast_form<5, 2, 1>(),     fast_form<5, 2, 2>(),
+    fast_form<7, 1, 0>(),                               fast_form<7, 1, 2>(),
+    fast_form<9, 1, 0>(),
+};
 
 }  // namespace
 
-int srn_conv_fast_launch(const SrnConvParams& p, int tile, int ksplit, hipStream_t stream) {
-  const bool x6 = p.precision == SRN_PREC_BF16X6;
-  const bool f32 = p.precision != SRN_PREC_BF16X3 && !x6;
-  const bool wpl = srn_weight_planes(p);
-  if (ksplit > 1) {  // split-K launches always take the 64 x 64 tile (they exist because the grid is small)
-    SRN_CHECK_ARG(tile == 4, "conv_fast: K slices of tile %d", tile);
-    if (f32) return launch_fast<FCfg<64, 64, 32, 32, 2, 0>>(p, false, stream, ksplit);
-    if (x6) return launch_fast<FCfg<64, 64, 32, 32, 2, 2>>(p, wpl, stream, ksplit);
-    return launch_fast<FCfg<64, 64, 32, 32>>(p, wpl, stream, ksplit);
-  }
-  if (f32) {
-    switch (tile) {
-      case 1: return launch_fast<FCfg<128, 128, 64, 64, 2, 0>>(p, false, stream);
-      case 2: return launch_fast<FCfg<128, 64, 32, 64, 2, 0>>(p, false, stream);
-      case 3: return launch_fast<FCfg<64, 128, 32, 64, 2, 0>>(p, false, stream);
-      case 4: return launch_fast<FCfg<64, 64, 32, 32, 2, 0>>(p, false, stream);
-      case 5: return launch_fast<FCfg<128, 32, 32, 32, 2, 0>>(p, false, stream);
-      case 7: return launch_fast<FCfg<64, 64, 32, 32, 1, 0>>(p, false, stream);  // single LDS stage
-      case 9: return launch_fast<FCfg<64, 128, 32, 64, 1, 0>>(p, false, stream);
-      default: break;
-    }
-  } else if (x6) {
-    switch (tile) {
-      // one LDS stage (48 KB, three workgroups per CU); the two-stage form (96 KB, one per CU) measured 0-40 % slower
-      case 1: return launch_fast<FCfg<128, 128, 64, 64, 1, 2>>(p, wpl, stream);
-      case 2: return launch_fast<FCfg<128, 64, 32, 64, 2, 2>>(p, wpl, stream);
-      case 3: return launch_fast<FCfg<64, 128, 32, 64, 2, 2>>(p, wpl, stream);
-      case 4: return launch_fast<FCfg<64, 64, 32, 32, 2, 2>>(p, wpl, stream);
-      case 5: return launch_fast<FCfg<128, 32, 32, 32, 2, 2>>(p, wpl, stream);
-      case 7: return launch_fast<FCfg<64, 64, 32, 32, 1, 2>>(p, wpl, stream);
-      default: break;
-    }
-  } else {
-    switch (tile) {
-      case 1: return launch_fast<FCfg<128, 128, 64, 64>>(p, wpl, stream);
-      case 2: return launch_fast<FCfg<128, 64, 32, 64>>(p, wpl, stream);
-      case 3: return launch_fast<FCfg<64, 128, 32, 64>>(p, wpl, stream);
-      case 4: return launch_fast<FCfg<64, 64, 32, 32>>(p, wpl, stream);
-      case 5: return launch_fast<FCfg<128, 32, 32, 32>>(p, wpl, stream);
-      default: break;
-    }
-  }
-  srn_set_error("conv_fast: no tile id %d in precision %d", tile, p.precision);
-  return -1;
-}
+SrnFormList srn_conv_fast_forms() { return kFastForms; }

@@ -36,16 +36,6 @@ struct Cfg {
   static constexpr int B_LD = BN / 32;
 };
 
-__device__ __forceinline__ float4 act4(float4 v, int act, float slope) {
-  if (act != SRN_ACT_NONE) {
-    v.x = srn_act(v.x, act, slope);
-    v.y = srn_act(v.y, act, slope);
-    v.z = srn_act(v.z, act, slope);
-    v.w = srn_act(v.w, act, slope);
-  }
-  return v;
-}
-
 // ACT: prologue activation compiled in: SRN_ACT_NONE, SRN_ACT_LEAKY, or -1 = decided at run time (SiLU / Mish:
 // only the tiny time-embedding GEMMs use those, so only the small tile is instantiated with -1).
 // PREC: 0 = exact fp32 MFMA (v_mfma_f32_32x32x2_f32); 1 = split-bf16: every fp32 operand is staged in LDS as a
@@ -177,10 +167,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const SrnConvParams p
       for (int i = 0; i < C::A_LD; ++i) {
         float4 v = sel4((R.a_ok >> i) & 1u, R.pa[i]);
         if constexpr (ACT == SRN_ACT_LEAKY) {
-          v.x = v.x > 0.f ? v.x : v.x * pro_slope;
-          v.y = v.y > 0.f ? v.y : v.y * pro_slope;
-          v.z = v.z > 0.f ? v.z : v.z * pro_slope;
-          v.w = v.w > 0.f ? v.w : v.w * pro_slope;
+          v = leaky4(v, pro_slope);
         } else if constexpr (ACT < 0) {
           v = act4(v, pro_act, pro_slope);
         }
@@ -226,10 +213,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const SrnConvParams p
       float4 v = sel4((R.a_ok >> i) & 1u, R.pa[i]);
       // act(0) == 0 for every supported activation, so masked rows stay zero
       if constexpr (ACT == SRN_ACT_LEAKY) {
-        v.x = v.x > 0.f ? v.x : v.x * pro_slope;
-        v.y = v.y > 0.f ? v.y : v.y * pro_slope;
-        v.z = v.z > 0.f ? v.z : v.z * pro_slope;
-        v.w = v.w > 0.f ? v.w : v.w * pro_slope;
+        v = leaky4(v, pro_slope);
       } else if constexpr (ACT < 0) {
         v = act4(v, pro_act, pro_slope);
       }
@@ -409,13 +393,10 @@ template <class C, int ACT, int PREC>
 int launch_prec(const SrnConvParams& p, hipStream_t stream) {
   constexpr int SMEM = PREC == 1 ? 2 * (C::BM + C::BN) * 128 : C::SMEM_BYTES;
   static SrnSmemAttr smem_attr;
-  if (const int e = smem_attr.ensure(reinterpret_cast<const void*>(&conv_gemm_kernel<C, ACT, PREC>), SMEM)) return e;
-  const int m_tiles = (p.T_out + C::BM - 1) / C::BM;
-  const int n_tiles = (p.N + C::BN - 1) / C::BN;
-  const int64_t blocks = (int64_t)p.n_batch * p.n_head * m_tiles * n_tiles;
-  SRN_CHECK_ARG(blocks > 0 && blocks < (1ll << 31), "conv_gemm: bad grid %lld", (long long)blocks);
-  hipLaunchKernelGGL((conv_gemm_kernel<C, ACT, PREC>), dim3((unsigned)blocks), dim3(256), SMEM, stream, p, m_tiles,
-                     n_tiles);
+  SrnTileGrid g;
+  if (const int e = srn_tile_grid<C>("conv_gemm", smem_attr, &conv_gemm_kernel<C, ACT, PREC>, SMEM, p, 1, 1ll << 31, g)) return e;
+  hipLaunchKernelGGL((conv_gemm_kernel<C, ACT, PREC>), dim3((unsigned)g.blocks), dim3(256), SMEM, stream, p, g.m_tiles,
+                     g.n_tiles);
   SRN_CHECK_LAUNCH();
   return 0;
 }
@@ -426,60 +407,73 @@ int launch_act(const SrnConvParams& p, hipStream_t stream) {
   return launch_prec<C, ACT, 0>(p, stream);
 }
 
-template <class C>
-int launch(const SrnConvParams& p, hipStream_t stream) {
+// RT_ACT: the form also has the run-time prologue activation (SiLU / Mish): the small tile only
+template <class C, bool RT_ACT = false>
+int launch(const SrnConvParams& p, int, hipStream_t stream) {
   if (p.pro_act == SRN_ACT_NONE) return launch_act<C, SRN_ACT_NONE>(p, stream);
-  return launch_act<C, SRN_ACT_LEAKY>(p, stream);
-}
-
-// the generic kernel of this file: any shape the validation lets through
-int conv_generic_launch(const SrnConvParams& p, int tile, hipStream_t stream) {
-  if (!(p.pro_act == SRN_ACT_NONE || p.pro_act == SRN_ACT_LEAKY)) {
-    // SiLU / Mish prologue: run-time activation, small tile only
-    SRN_CHECK_ARG(tile == 4, "conv_gemm: run-time activation on tile %d", tile);
-    return p.w_nmajor ? launch_act<Cfg<64, 64, 32, 32, true>, -1>(p, stream)
-                      : launch_act<Cfg<64, 64, 32, 32, false>, -1>(p, stream);
-  }
-  if (p.w_nmajor) {
-    switch (tile) {
-      case 1: return launch<Cfg<128, 128, 64, 64, true>>(p, stream);
-      case 3: return launch<Cfg<64, 128, 32, 64, true>>(p, stream);
-      case 4: return launch<Cfg<64, 64, 32, 32, true>>(p, stream);
-      default: break;
-    }
-  } else {
-    switch (tile) {
-      case 1: return launch<Cfg<128, 128, 64, 64, false>>(p, stream);
-      case 2: return launch<Cfg<128, 64, 32, 64, false>>(p, stream);
-      case 3: return launch<Cfg<64, 128, 32, 64, false>>(p, stream);
-      case 4: return launch<Cfg<64, 64, 32, 32, false>>(p, stream);
-      case 5: return launch<Cfg<128, 32, 32, 32, false>>(p, stream);
-      default: break;
-    }
-  }
-  srn_set_error("conv_gemm: no tile id %d", tile);
+  if (p.pro_act == SRN_ACT_LEAKY) return launch_act<C, SRN_ACT_LEAKY>(p, stream);
+  if constexpr (RT_ACT) return launch_act<C, -1>(p, stream);
+  srn_set_error("conv_gemm: run-time activation on a %d x %d tile", C::BM, C::BN);
   return -1;
 }
+
+// The generic kernel of this file: any shape the validation lets through, k-major (KM) or n-major (NM) B.  Its fp32 rows
+// serve bf16x6 too (form_precision below).  Id 4 is the small tile with the run-time activation.
+template <int ID, bool NMAJ>
+constexpr SrnConvForm gform(int precision) {
+  using C = Cfg<SRN_TILE(ID), NMAJ>;
+  return srn_form<ID, C>(precision, NMAJ, 2, false, launch<C, ID == 4>);
+}
+constexpr int F32 = SRN_PREC_FP32, X3 = SRN_PREC_BF16X3;
+constexpr bool KM = false, NM = true;
+constexpr SrnConvForm kGenericForms[] = {
+    gform<1, KM>(F32), gform<1, KM>(X3), gform<1, NM>(F32), gform<1, NM>(X3),
+    gform<2, KM>(F32), gform<2, KM>(X3),
+    gform<3, KM>(F32), gform<3, KM>(X3), gform<3, NM>(F32), gform<3, NM>(X3),
+    gform<4, KM>(F32), gform<4, KM>(X3), gform<4, NM>(F32), gform<4, NM>(X3),
+    gform<5, KM>(F32), gform<5, KM>(X3),
+};
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Kernel choice.  conv_route is a pure function of the (validated) params: no device is touched, so the CPU test suite
 // asks it (srn_conv_gemm_route) which kernel every op of a plan gets.
 
-// family bits of the tile table (conv_fast.hip's forms differ per precision; the generic kernel per B layout)
-enum : unsigned {
-  HAS_F32 = 1,                                      // conv_f32.hip
-  HAS_FAST_FP32 = 2, HAS_FAST_X3 = 4, HAS_FAST_X6 = 8,  // conv_fast.hip
-  HAS_FAST = HAS_FAST_FP32 | HAS_FAST_X3 | HAS_FAST_X6,
-  HAS_HALO = 16,                                    // conv_halo.hip (split-bf16 only)
-  HAS_GENERIC = 32, HAS_GENERIC_NMAJ = 64,          // this file, k-major / n-major weights
-};
+// A family's forms, from its own file's list (conv_common.h: SrnConvForm), in the order of SRN_FAMILY_*.
+const SrnFormList& family_forms(int family) {
+  static const SrnFormList lists[] = {srn_conv_generic_forms(), srn_conv_f32_forms(), srn_conv_fast_forms(),
+                                      srn_conv_halo_forms(), srn_conv_strip_forms()};
+  static_assert(SRN_FAMILY_GENERIC == 0 && SRN_FAMILY_F32 == 1 && SRN_FAMILY_FAST == 2 && SRN_FAMILY_HALO == 3 &&
+                SRN_FAMILY_STRIP == 4, "the order of the lists");
+  return lists[family];
+}
 
+// the arithmetic a family's rows are looked up under: the generic kernel runs bf16x6 on its fp32 path
+int form_precision(int family, int precision) {
+  if (precision == SRN_PREC_BF16X3) return precision;
+  return precision == SRN_PREC_BF16X6 && family != SRN_FAMILY_GENERIC ? precision : SRN_PREC_FP32;
+}
+
+// the family's form of tile id `tile` for p's arithmetic and B layout, nullptr if it has none
+const SrnConvForm* find_form(int family, const SrnConvParams& p, int tile) {
+  const SrnFormList& l = family_forms(family);
+  for (const SrnConvForm* f = l.rows; f != l.rows + l.n; ++f)
+    if (f->tile == tile && f->precision == form_precision(family, p.precision) && f->nmajor == (p.w_nmajor != 0)) return f;
+  return nullptr;
+}
+
+// the tile id of the family's form for K slices in p's arithmetic, 0 if it has none
+int kslice_tile(int family, const SrnConvParams& p) {
+  const SrnFormList& l = family_forms(family);
+  for (const SrnConvForm* f = l.rows; f != l.rows + l.n; ++f)
+    if (f->kslices && f->precision == form_precision(family, p.precision)) return f->tile;
+  return 0;
+}
+
+// What the route adds to a tile id (its geometry is conv_common.h's kSrnTileGeom[id], its forms the families' lists).
 struct TileInfo {
-  int id, bm, bn, wm, wn, stages;  // output tile, per-wave tile, LDS stages of the conv_fast.hip / generic form
-  unsigned has;                    // families with a form of this id
-  int twin;                        // what a family without this id runs instead (0: it does not take the launch)
-  float base[3];                   // measured relative efficiency of the tile shape on large grids: [fp32, split-bf16,
-                                   // bf16x6]; pick_tile's model chooses among the ids that have one
+  int twin;       // what a family without a form of this id runs instead (0: it does not take the launch)
+  float base[3];  // measured relative efficiency of the tile shape on large grids: [fp32, split-bf16, bf16x6];
+                  // pick_tile's model chooses among the ids that have one
 };
 // (priors from tools/opbench.py --sweep on MI355X: in fp32 the MFMA phase is long and the small tile loses nothing;
 //  in split-bf16 the kernel is L2-traffic sensitive and bigger tiles win)
@@ -489,39 +483,26 @@ struct TileInfo {
 // wave pairs, 11 loads two steps ahead (small grids, split-K slices).  In exact fp32, id 4 (the small-grid 64 x 64) is
 // conv_f32.hip's 11 (B = 1 x T = 256: 16.8 -> 15.8 ms against conv_fast.hip's double-buffered tile).  Ids 6 and 8
 // (single-stage 128 x 128 / 128 x 64) are never chosen and have no kernel: forced, they run their twins.
-const TileInfo kTiles[] = {
-    {1, 128, 128, 64, 64, 2, HAS_FAST | HAS_HALO | HAS_GENERIC | HAS_GENERIC_NMAJ, 0, {1.00f, 1.00f, 1.00f}},
-    {2, 128, 64, 32, 64, 2, HAS_FAST | HAS_HALO | HAS_GENERIC, 0, {0.90f, 0.95f, 0.95f}},
-    {3, 64, 128, 32, 64, 2, HAS_FAST | HAS_HALO | HAS_GENERIC | HAS_GENERIC_NMAJ, 0, {0.92f, 0.97f, 0.97f}},
-    {4, 64, 64, 32, 32, 2, HAS_FAST | HAS_HALO | HAS_GENERIC | HAS_GENERIC_NMAJ, 11, {0.97f, 0.85f, 0.90f}},
-    {5, 128, 32, 32, 32, 2, HAS_F32 | HAS_FAST | HAS_HALO | HAS_GENERIC, 0, {0.85f, 0.75f, 0.80f}},
-    {6, 128, 128, 64, 64, 1, 0, 1, {}},
-    {7, 64, 64, 32, 32, 1, HAS_F32 | HAS_FAST_FP32 | HAS_FAST_X6, 4, {}},
-    {8, 128, 64, 32, 64, 1, 0, 2, {}},
-    {9, 64, 128, 32, 64, 1, HAS_F32 | HAS_FAST_FP32, 3, {}},
-    {10, 32, 64, 32, 32, 1, HAS_F32, 7, {}},
-    {11, 64, 64, 32, 32, 1, HAS_F32, 4, {}},
+const TileInfo kTiles[SRN_TILE_IDS] = {
+    /* 0 */ {},
+    /* 1 */ {0, {1.00f, 1.00f, 1.00f}},
+    /* 2 */ {0, {0.90f, 0.95f, 0.95f}},
+    /* 3 */ {0, {0.92f, 0.97f, 0.97f}},
+    /* 4 */ {11, {0.97f, 0.85f, 0.90f}},
+    /* 5 */ {0, {0.85f, 0.75f, 0.80f}},
+    /* 6 */ {1, {}}, /* 7 */ {4, {}}, /* 8 */ {2, {}}, /* 9 */ {3, {}}, /* 10 */ {7, {}}, /* 11 */ {4, {}},
 };
 
-const TileInfo* tile_info(int id) {
-  for (const TileInfo& t : kTiles)
-    if (t.id == id) return &t;
-  return nullptr;
-}
+// an id the route knows (0 is the strip kernel's, which takes no tile id)
+bool known_tile(int id) { return id >= 1 && id < SRN_TILE_IDS; }
 
 // the id a family runs for `id`: the id itself, else the first twin down the table's chain it has, else 0
-int tile_form(unsigned family, int id) {
-  for (int hop = 0; hop < 3; ++hop) {
-    const TileInfo* t = tile_info(id);
-    if (t == nullptr) return 0;
-    if (t->has & family) return id;
-    id = t->twin;
+int tile_form(int family, const SrnConvParams& p, int id) {
+  for (int hop = 0; hop < 3 && known_tile(id); ++hop) {
+    if (find_form(family, p, id)) return id;
+    id = kTiles[id].twin;
   }
   return 0;
-}
-
-unsigned fast_family(int precision) {
-  return precision == SRN_PREC_BF16X3 ? HAS_FAST_X3 : precision == SRN_PREC_BF16X6 ? HAS_FAST_X6 : HAS_FAST_FP32;
 }
 
 int pick_tile(const SrnConvParams& p) {
@@ -553,24 +534,26 @@ int pick_tile(const SrnConvParams& p) {
   int best_id = 4;
   const double z = (double)p.n_batch * p.n_head;
   const double cus = SRN_NUM_CUS;
-  for (const TileInfo& t : kTiles) {
+  for (int id = 1; id < SRN_TILE_IDS; ++id) {
+    const TileInfo& t = kTiles[id];
     if (t.base[0] == 0.f) continue;
-    if (p.geglu && t.wn < 64) continue;
-    if (p.w_nmajor && !(t.has & HAS_GENERIC_NMAJ)) continue;
-    const double mt = (p.T_out + t.bm - 1) / t.bm, nt = (p.N + t.bn - 1) / t.bn;
+    const SrnTileGeom& g = kSrnTileGeom[id];
+    if (p.geglu && g.wn < 64) continue;
+    if (p.w_nmajor && !find_form(SRN_FAMILY_GENERIC, p, id)) continue;
+    const double mt = (p.T_out + g.bm - 1) / g.bm, nt = (p.N + g.bn - 1) / g.bn;
     const double blocks = z * mt * nt;
-    const double useful = ((double)p.T_out * p.N) / (mt * t.bm * nt * t.bn);
+    const double useful = ((double)p.T_out * p.N) / (mt * g.bm * nt * g.bn);
     const double rounds = (blocks + (cus - 1.0)) / cus;
     double quant = blocks / (cus * (double)(int64_t)rounds);
     // fewer blocks than CUs idles CUs outright; beyond one round, co-resident blocks absorb part of the tail
     if (blocks > cus) quant = 0.35 + 0.65 * quant;
     float score = (float)(useful * quant) * t.base[p.precision == SRN_PREC_BF16X3 ? 1 : (p.precision == SRN_PREC_BF16X6 ? 2 : 0)];
     // both operands split in the loop (Q K^T, P V): the 64x128 tile measured 5-10 % ahead of 128x128
-    if (p.precision == SRN_PREC_BF16X3 && (p.w_hi == nullptr || p.w_bs != 0 || p.w_hs != 0) && t.id == 1)
+    if (p.precision == SRN_PREC_BF16X3 && (p.w_hi == nullptr || p.w_bs != 0 || p.w_hs != 0) && id == 1)
       score *= 0.92f;
     if (score > best) {
       best = score;
-      best_id = t.id;
+      best_id = id;
     }
   }
   // bf16x6: wherever the model settles on the 64 x 64 tile, its single-stage form (id 7) is ahead on every shape of the
@@ -606,7 +589,7 @@ bool f32_takes(const SrnConvParams& p, int tile, int ksplit) {
   if ((rows_all * p.ld_out + p.N) * 4 >= lim || (rows_all * p.ld_res + p.N) * 4 >= lim ||
       (rows_all * p.ld_res2 + p.N) * 4 >= lim)
     return false;
-  const TileInfo& t = *tile_info(tile);
+  const SrnTileGeom& t = kSrnTileGeom[tile];
   const int64_t blocks = (int64_t)p.n_batch * p.n_head * ((p.T_out + t.bm - 1) / t.bm) * ((p.N + t.bn - 1) / t.bn) * ksplit;
   return blocks < (1ll << 26);
 }
@@ -634,8 +617,7 @@ bool halo_takes(const SrnConvParams& p, int tile) {
   if (p.precision != SRN_PREC_BF16X3 || p.n_taps < 2 || p.in_stride != 1 || p.pad_reflect || p.w_nmajor || p.geglu)
     return false;
   if (!(p.pro_act == SRN_ACT_NONE || p.pro_act == SRN_ACT_LEAKY)) return false;
-  const TileInfo* t = tile_info(tile);
-  if (t == nullptr || !(t->has & HAS_HALO)) return false;
+  if (find_form(SRN_FAMILY_HALO, p, tile) == nullptr) return false;
   int lo = 0;
   if (srn_tap_span(p, lo) > SRN_HALO_MAX) return false;
   // Measured on MI355X (tools/opbench.py --bf16x3 [--no-halo]): the halo image pays off when it is reused by many
@@ -674,16 +656,16 @@ struct ConvRoute {
 int conv_route(const SrnConvParams& p, ConvRoute& r) {
   r = {SRN_FAMILY_GENERIC, 0, 1};
   int tile = p.tile > 0 ? p.tile : pick_tile(p);
-  const TileInfo* t = tile_info(tile);
-  if (p.geglu && (t == nullptr || t->wn < 64)) tile = 1;  // the gate pairs columns n, n + 32 inside one wave
+  if (p.geglu && (!known_tile(tile) || kSrnTileGeom[tile].wn < 64)) tile = 1;  // the gate pairs columns n, n + 32 inside one wave
   const bool fp32 = p.precision == SRN_PREC_FP32;
   const bool use_f32 = fp32 && p.route != SRN_ROUTE_FAST_FP32;
   if (p.ws != nullptr && p.tile <= 0 && p.route != SRN_ROUTE_GENERIC) {
     // small grids with a deep contraction (B = 1 / short utterances): slice K over extra workgroups, reduce after
     const int ks = splitk_plan(p);
     if (ks > 1 && p.ws_bytes >= srn_splitk_bytes(p, ks)) {
-      if (use_f32 && f32_takes(p, 11, ks)) r = {SRN_FAMILY_F32, 11, ks};
-      else r = {SRN_FAMILY_FAST, 4, ks};  // splitk_plan splits only what conv_fast.hip takes
+      const int f32_tile = use_f32 ? kslice_tile(SRN_FAMILY_F32, p) : 0;
+      if (f32_tile != 0 && f32_takes(p, f32_tile, ks)) r = {SRN_FAMILY_F32, f32_tile, ks};
+      else r = {SRN_FAMILY_FAST, kslice_tile(SRN_FAMILY_FAST, p), ks};  // splitk_plan splits only what conv_fast.hip takes
       return 0;
     }
   }
@@ -698,18 +680,18 @@ int conv_route(const SrnConvParams& p, ConvRoute& r) {
     }
   }
   if (p.route != SRN_ROUTE_GENERIC) {
-    const int f32_tile = use_f32 ? tile_form(HAS_F32, tile) : 0;
+    const int f32_tile = use_f32 ? tile_form(SRN_FAMILY_F32, p, tile) : 0;
     if (f32_tile != 0 && f32_takes(p, f32_tile, 1)) {
       r = {SRN_FAMILY_F32, f32_tile, 1};
       return 0;
     }
-    const int fast_tile = tile_form(fast_family(p.precision), tile);
+    const int fast_tile = tile_form(SRN_FAMILY_FAST, p, tile);
     if (fast_tile != 0 && fast_takes(p)) {
       r = {SRN_FAMILY_FAST, fast_tile, 1};
       return 0;
     }
   }
-  int gen_tile = tile_form(p.w_nmajor ? HAS_GENERIC_NMAJ : HAS_GENERIC, tile);
+  int gen_tile = tile_form(SRN_FAMILY_GENERIC, p, tile);
   if (gen_tile == 0 && p.w_nmajor) gen_tile = 4;  // the n-major forms fall back to 64 x 64
   SRN_CHECK_ARG(gen_tile != 0, "conv_gemm: unknown tile id %d", tile);
   // SiLU / Mish prologue: run-time activation, small tile only
@@ -768,22 +750,33 @@ int conv_params(const SrnConvParams* pp, SrnConvParams& p) {
 
 }  // namespace
 
+SrnFormList srn_conv_generic_forms() { return kGenericForms; }
+
 extern "C" int srn_conv_gemm(const SrnConvParams* pp, void* stream_) {
   SrnConvParams p;
   if (const int e = conv_params(pp, p)) return e;
   ConvRoute r;
   if (const int e = conv_route(p, r)) return e;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  int e = 0;
-  switch (r.family) {
-    case SRN_FAMILY_F32: e = srn_conv_f32_launch(p, r.tile, r.ksplit, stream); break;
-    case SRN_FAMILY_FAST: e = srn_conv_fast_launch(p, r.tile, r.ksplit, stream); break;
-    case SRN_FAMILY_HALO: e = srn_conv_halo_launch(p, r.tile, r.ksplit, stream); break;
-    case SRN_FAMILY_STRIP: e = srn_conv_strip_launch(p, r.tile, r.ksplit, stream); break;
-    default: e = conv_generic_launch(p, r.tile, stream); break;
-  }
+  const SrnConvForm* f = find_form(r.family, p, r.tile);
+  SRN_CHECK_ARG(f != nullptr, "conv_gemm: family %d has no tile id %d in precision %d", r.family, r.tile, p.precision);
+  SRN_CHECK_ARG(r.ksplit == 1 || f->kslices, "conv_gemm: %d K slices of family %d tile %d", r.ksplit, r.family, r.tile);
+  int e = f->launch(p, r.ksplit, stream);
   if (e == 0 && r.ksplit > 1) e = srn_splitk_reduce(p, r.ksplit, stream);
   return e;
+}
+
+extern "C" int srn_conv_gemm_forms(int32_t* rows, int capacity) {
+  int n = 0;
+  for (int family = SRN_FAMILY_GENERIC; family <= SRN_FAMILY_STRIP; ++family) {
+    const SrnFormList& l = family_forms(family);
+    for (const SrnConvForm* f = l.rows; f != l.rows + l.n; ++f, ++n) {
+      const SrnTileGeom& g = kSrnTileGeom[f->tile];
+      const int32_t row[SRN_FORM_FIELDS] = {family, f->tile, f->precision, f->nmajor, f->kslices, g.bm, g.bn, g.wn, f->stages};
+      for (int k = 0; rows != nullptr && n < capacity && k < SRN_FORM_FIELDS; ++k) rows[n * SRN_FORM_FIELDS + k] = row[k];
+    }
+  }
+  return n;
 }
 
 extern "C" int srn_conv_gemm_route(const SrnConvParams* pp, int32_t out[3]) {

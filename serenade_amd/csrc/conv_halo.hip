@@ -245,39 +245,32 @@ __global__ __launch_bounds__(256, 2) void conv_halo_kernel(const SrnConvParams p
 }
 
 template <class C, int ACT>
-int launch_halo(const SrnConvParams& p, int min_off, int halo, hipStream_t stream) {
+int launch_halo(const SrnConvParams& p, hipStream_t stream) {
+  int min_off = 0;
+  const int halo = srn_tap_span(p, min_off);
+  SRN_CHECK_ARG(halo <= HALO_MAX, "conv_halo: tap span %d", halo);
   static SrnSmemAttr smem_attr;
-  if (const int e = smem_attr.ensure(reinterpret_cast<const void*>(&conv_halo_kernel<C, ACT>), C::SMEM_BYTES)) return e;
-  const int m_tiles = (p.T_out + C::BM - 1) / C::BM;
-  const int n_tiles = (p.N + C::BN - 1) / C::BN;
-  const int64_t blocks = (int64_t)p.n_batch * p.n_head * m_tiles * n_tiles;
-  SRN_CHECK_ARG(blocks > 0 && blocks < (1ll << 31), "conv_halo: bad grid %lld", (long long)blocks);
-  hipLaunchKernelGGL((conv_halo_kernel<C, ACT>), dim3((unsigned)blocks), dim3(256), C::SMEM_BYTES, stream, p, m_tiles,
-                     n_tiles, min_off, halo);
+  SrnTileGrid g;
+  if (const int e = srn_tile_grid<C>("conv_halo", smem_attr, &conv_halo_kernel<C, ACT>, C::SMEM_BYTES, p, 1, 1ll << 31, g))
+    return e;
+  hipLaunchKernelGGL((conv_halo_kernel<C, ACT>), dim3((unsigned)g.blocks), dim3(256), C::SMEM_BYTES, stream, p, g.m_tiles,
+                     g.n_tiles, min_off, halo);
   SRN_CHECK_LAUNCH();
   return 0;
 }
 
 template <class C>
-int launch_halo_act(const SrnConvParams& p, int min_off, int halo, hipStream_t stream) {
-  if (p.pro_act == SRN_ACT_LEAKY) return launch_halo<C, SRN_ACT_LEAKY>(p, min_off, halo, stream);
-  return launch_halo<C, SRN_ACT_NONE>(p, min_off, halo, stream);
+int launch_halo_act(const SrnConvParams& p, int, hipStream_t stream) {
+  if (p.pro_act == SRN_ACT_LEAKY) return launch_halo<C, SRN_ACT_LEAKY>(p, stream);
+  return launch_halo<C, SRN_ACT_NONE>(p, stream);
 }
+
+template <int ID>
+constexpr SrnConvForm halo_form() {
+  return srn_form<ID, HCfg<SRN_TILE(ID)>>(SRN_PREC_BF16X3, false, 2, false, launch_halo_act<HCfg<SRN_TILE(ID)>>);
+}
+constexpr SrnConvForm kHaloForms[] = {halo_form<1>(), halo_form<2>(), halo_form<3>(), halo_form<4>(), halo_form<5>()};
 
 }  // namespace
 
-int srn_conv_halo_launch(const SrnConvParams& p, int tile, int ksplit, hipStream_t stream) {
-  int lo = 0;
-  const int halo = srn_tap_span(p, lo);
-  SRN_CHECK_ARG(ksplit == 1 && halo <= HALO_MAX, "conv_halo: tap span %d, %d K slices", halo, ksplit);
-  switch (tile) {
-    case 1: return launch_halo_act<HCfg<128, 128, 64, 64>>(p, lo, halo, stream);
-    case 2: return launch_halo_act<HCfg<128, 64, 32, 64>>(p, lo, halo, stream);
-    case 3: return launch_halo_act<HCfg<64, 128, 32, 64>>(p, lo, halo, stream);
-    case 4: return launch_halo_act<HCfg<64, 64, 32, 32>>(p, lo, halo, stream);
-    case 5: return launch_halo_act<HCfg<128, 32, 32, 32>>(p, lo, halo, stream);
-    default: break;
-  }
-  srn_set_error("conv_halo: no tile id %d", tile);
-  return -1;
-}
+SrnFormList srn_conv_halo_forms() { return kHaloForms; }

@@ -164,7 +164,7 @@ int launch_strip(const SrnConvParams& p, int min_off, int halo, hipStream_t stre
   int per_cu = (156 * 1024) / smem;
   per_cu = per_cu < 1 ? 1 : per_cu;  // workgroups that fit a CU's 160 KB (register use allows up to 4 waves per SIMD for C_in 32)
   per_cu = per_cu > 4 ? 4 : per_cu;
-  const int grid = (int)(n_tiles < 256 * per_cu ? n_tiles : 256 * per_cu);
+  const int grid = (int)(n_tiles < SRN_NUM_CUS * per_cu ? n_tiles : SRN_NUM_CUS * per_cu);
   hipLaunchKernelGGL((conv_strip_kernel<CIN, NT, ACT>), dim3(grid), dim3(256), smem, stream, p, min_off, halo,
                      tiles_per_z, (int)n_tiles);
   SRN_CHECK_LAUNCH();
@@ -177,15 +177,21 @@ int launch_strip_act(const SrnConvParams& p, int min_off, int halo, hipStream_t 
   return launch_strip<CIN, NT, SRN_ACT_NONE>(p, min_off, halo, stream);
 }
 
-}  // namespace
-
-int srn_conv_strip_launch(const SrnConvParams& p, int, int ksplit, hipStream_t stream) {
+// the one form of this file: which of the four (C_in, N) kernels runs follows from the params
+int launch_strip_any(const SrnConvParams& p, int, hipStream_t stream) {
   int lo = 0;
   const int halo = srn_tap_span(p, lo);
-  SRN_CHECK_ARG(ksplit == 1 && halo <= HALO_MAX && (p.C_in == 32 || p.C_in == 64) && (p.N == 32 || p.N == 64),
-                "conv_strip: C_in %d, N %d, tap span %d, %d K slices", p.C_in, p.N, halo, ksplit);
+  SRN_CHECK_ARG(halo <= HALO_MAX && (p.C_in == 32 || p.C_in == 64) && (p.N == 32 || p.N == 64),
+                "conv_strip: C_in %d, N %d, tap span %d", p.C_in, p.N, halo);
   if (p.C_in == 32 && p.N == 32) return launch_strip_act<32, 1>(p, lo, halo, stream);
   if (p.C_in == 32 && p.N == 64) return launch_strip_act<32, 2>(p, lo, halo, stream);
   if (p.C_in == 64 && p.N == 32) return launch_strip_act<64, 1>(p, lo, halo, stream);
   return launch_strip_act<64, 2>(p, lo, halo, stream);
 }
+
+static_assert(BM == kSrnTileGeom[0].bm, "tile id 0 is this kernel's");
+constexpr SrnConvForm kStripForms[] = {{0, SRN_PREC_BF16X3, false, 1, false, launch_strip_any}};
+
+}  // namespace
+
+SrnFormList srn_conv_strip_forms() { return kStripForms; }

@@ -6,9 +6,9 @@ the cross-compiled library) and tests/test_hip_convsweep.py (MI355X: the kernels
 is touched here.  Buf / Out / Case / materialize / check_outputs are those of tests/_rowop_cases.py.
 
 A case is the keyword dict of one ``ops.ConvOp`` (``Case.args`` holds its items; ``kwargs`` turns materialized args
-back into the dict).  It forces ``tile``, ``route`` and ``precision`` so that it reaches ONE kernel form (FORMS below:
-tests/test_conv_route.KERNELS, told apart further by weight planes / operands split in the loop, by the n-major generic
-forms and by ROUTE_FAST_FP32; the split-K slices of both families are forms of their own).  Every tensor the call writes
+back into the dict).  It forces ``tile``, ``route`` and ``precision`` so that it reaches ONE kernel form (forms() below:
+the rows of the library's own list, srn_conv_gemm_forms, told apart further by weight planes / operands split in the
+loop and by ROUTE_FAST_FP32; the split-K slices of both families are forms of their own).  Every tensor the call writes
 (out, out_tr, gn_partials, in-place res / res2) is a Buf between guard bands; ld padding columns, rows not congruent to
 out_t_off mod out_t_stride, out_tr columns at or past T_out and the columns of `out` at or past out_tr_col0 start as
 sentinels (or, in place, as their input values) and must come back bit for bit.  Rows at or past len_out must be exactly
@@ -68,18 +68,22 @@ TOL = {
 }
 CASE_TOL = {}  # (form, case id) -> (baseline, tolerance): none needed
 
-# tile id -> (bm, bn, wn) of conv_gemm.hip's kTiles
-TILES = {1: (128, 128, 64), 2: (128, 64, 64), 3: (64, 128, 64), 4: (64, 64, 32), 5: (128, 32, 32), 7: (64, 64, 32),
-         9: (64, 128, 64), 10: (32, 64, 32), 11: (64, 64, 32)}
-
 
 class Form:
-    """one kernel form: what the route must answer (family, tile, K slices > 1) and how a case forces it"""
+    """one kernel form: what the route must answer (family, tile, K slices > 1), how a case forces it, and the tile
+    geometry of its row in the library's list"""
 
-    def __init__(self, name, family, tile, prec, route, planes=False, nmajor=False, splitk=False):
-        self.name, self.family, self.tile, self.prec, self.route = name, family, tile, prec, route
-        self.planes, self.nmajor, self.splitk = planes, nmajor, splitk
-        self.bm, self.bn, self.wn = (128, 64, 32) if family == "strip" else TILES[tile]
+    def __init__(self, row, family, tile, prec, planes, nmajor, splitk):
+        self.family, self.tile, self.prec, self.planes, self.nmajor, self.splitk = family, tile, prec, planes, nmajor, splitk
+        self.bm, self.bn, self.wn = row.bm, row.bn, row.wn
+        p = PREC_NAME[prec]
+        self.route = {"generic": _lib.ROUTE_GENERIC, "f32": _lib.ROUTE_AUTO, "halo": _lib.ROUTE_HALO, "strip": _lib.ROUTE_STRIP,
+                      "fast": _lib.ROUTE_FAST_FP32 if prec == FP32 else _lib.ROUTE_TILED}[family]
+        self.name = {"generic": f"generic{tile}-{'nmaj-' if nmajor else ''}{p}", "f32": f"f32-{tile}", "halo": f"halo{tile}",
+                     "fast": f"fast{tile}-{p}" + ("" if prec == FP32 else "-planes" if planes else "-loop"),
+                     "strip": "strip"}[family]
+        if splitk:
+            self.name = "splitk-f32" if family == "f32" else f"splitk-fast-{p}"
 
     @property
     def key(self):
@@ -87,31 +91,26 @@ class Form:
         return (self.family, self.tile, self.prec, self.planes, self.nmajor, self.splitk)
 
 
+def _keys(row):
+    """the Form.key s the sweep makes of one row of the library's list: conv_fast.hip's split-bf16 forms with weight
+    planes and with operands split in the loop are forms of their own (the strip kernel has planes only), and so are
+    the K slices of a row that takes them (with planes, where the arithmetic has them)"""
+    from tests.test_conv_route import FAMILY
+    fam = FAMILY[row.family]
+    split = fam == "fast" and row.precision != FP32
+    for planes in ((True, False) if split else (fam == "strip",)):
+        yield (fam, row.tile, row.precision, planes, bool(row.nmajor), False)
+    if row.kslices:
+        yield (fam, row.tile, row.precision, split, bool(row.nmajor), True)
+
+
 def _forms():
-    from tests.test_conv_route import KERNELS
-    out = []
-    for t in sorted(KERNELS["generic"]):
-        for prec in (FP32, X3):  # bf16x6 runs the generic kernel's fp32 path
-            out.append(Form(f"generic{t}-{PREC_NAME[prec]}", "generic", t, prec, _lib.ROUTE_GENERIC))
-            if t in (1, 3, 4):
-                out.append(Form(f"generic{t}-nmaj-{PREC_NAME[prec]}", "generic", t, prec, _lib.ROUTE_GENERIC, nmajor=True))
-    for t in sorted(KERNELS[("f32", FP32)]):
-        out.append(Form(f"f32-{t}", "f32", t, FP32, _lib.ROUTE_AUTO))
-    for t in sorted(KERNELS[("fast", FP32)]):
-        out.append(Form(f"fast{t}-fp32", "fast", t, FP32, _lib.ROUTE_FAST_FP32))
-    for prec in (X3, X6):
-        for t in sorted(KERNELS[("fast", prec)]):
-            for planes in (True, False):
-                out.append(Form(f"fast{t}-{PREC_NAME[prec]}-{'planes' if planes else 'loop'}", "fast", t, prec,
-                                _lib.ROUTE_TILED, planes=planes))
-    for t in sorted(KERNELS["halo"]):
-        out.append(Form(f"halo{t}", "halo", t, X3, _lib.ROUTE_HALO))
-    out.append(Form("strip", "strip", 0, X3, _lib.ROUTE_STRIP, planes=True))
-    out.append(Form("splitk-f32", "f32", 11, FP32, _lib.ROUTE_AUTO, splitk=True))
-    out.append(Form("splitk-fast-fp32", "fast", 4, FP32, _lib.ROUTE_FAST_FP32, splitk=True))
-    out.append(Form("splitk-fast-bf16x3", "fast", 4, X3, _lib.ROUTE_TILED, planes=True, splitk=True))
-    out.append(Form("splitk-fast-bf16x6", "fast", 4, X6, _lib.ROUTE_TILED, planes=True, splitk=True))
-    return out
+    from tests.test_conv_route import library_forms
+    # generic: by tile, the n-major form after the k-major one; conv_fast.hip: by arithmetic; the K slices last
+    rows = sorted(library_forms(), key=lambda r: (r.family, r.precision if r.family == _lib.FAMILY_FAST else 0, r.tile,
+                                                  r.precision, r.nmajor))
+    keyed = [(r, k) for r in rows for k in _keys(r)]
+    return [Form(r, *k) for splitk in (False, True) for r, k in keyed if k[5] == splitk]
 
 
 _FORMS = None
@@ -125,29 +124,10 @@ def forms():
 
 
 def existing_forms():
-    """the set of Form.key a kernel exists for, from the launchers' switches (tests/test_conv_route.KERNELS) and the
-    distinctions of this module's docstring: what the sweep must reach, no more and no less"""
-    from tests.test_conv_route import KERNELS
-    want = set()
-    for t in KERNELS["generic"]:
-        for prec in (FP32, X3):
-            want.add(("generic", t, prec, False, False, False))
-    for t in (1, 3, 4):
-        for prec in (FP32, X3):
-            want.add(("generic", t, prec, False, True, False))
-    for t in KERNELS[("f32", FP32)]:
-        want.add(("f32", t, FP32, False, False, False))
-    for t in KERNELS[("fast", FP32)]:
-        want.add(("fast", t, FP32, False, False, False))
-    for prec in (X3, X6):
-        for t in KERNELS[("fast", prec)]:
-            want |= {("fast", t, prec, True, False, False), ("fast", t, prec, False, False, False)}
-    for t in KERNELS["halo"]:
-        want.add(("halo", t, X3, False, False, False))
-    want.add(("strip", 0, X3, True, False, False))
-    want |= {("f32", 11, FP32, False, False, True), ("fast", 4, FP32, False, False, True),
-             ("fast", 4, X3, True, False, True), ("fast", 4, X6, True, False, True)}
-    return want
+    """the set of Form.key a kernel exists for, from the library's list and the distinctions of _keys: what the sweep
+    must reach, no more and no less"""
+    from tests.test_conv_route import library_forms
+    return {k for r in library_forms() for k in _keys(r)}
 
 
 # ------------------------------------------------------------------------------------------------------- the matrix

@@ -1,14 +1,18 @@
 """CPU checks of srn_conv_gemm's kernel choice (conv_gemm.hip's conv_route, exported as srn_conv_gemm_route): which
 kernel family, tile id and K-slice count every contraction of the inference plans and of the training step's forward
-gets, against the committed table tests/conv_routes.json; and invariants of the route over a sweep of shapes.
+gets, against the committed table tests/conv_routes.json; invariants of the route over a sweep of shapes; and the
+kernel forms the library lists (srn_conv_gemm_forms: what its launch and its route read) against the committed snapshot
+tests/conv_forms.json.
 
 The plans are built under the kernel emulator (tests/_emulator.py); the route is asked for each ConvOp's params as the
 GPU build would fill them: weight planes attached in the split-bf16 modes and the split-K workspace attached where the
 library asks for one (ops.ConvOp._build).
 
-    python -m tests.test_conv_route   # prints the table for tests/conv_routes.json
+    python -m tests.test_conv_route         # prints the table for tests/conv_routes.json
+    python -m tests.test_conv_route forms   # prints the snapshot for tests/conv_forms.json
 """
 import ctypes
+import functools
 import json
 import os
 
@@ -23,6 +27,7 @@ from tests import _emulator
 from tests._weights import serenade_weights, sub
 
 TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "conv_routes.json")
+FORMS_TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "conv_forms.json")
 FAMILY = {_lib.FAMILY_GENERIC: "generic", _lib.FAMILY_F32: "f32", _lib.FAMILY_FAST: "fast", _lib.FAMILY_HALO: "halo",
           _lib.FAMILY_STRIP: "strip"}
 # (plan, precision): inference plans of bench.py's headline (B = 8 x T = 1024, 256 prompt frames) and its B = 1 x T = 256
@@ -144,13 +149,35 @@ def test_route_validates_like_the_launch(lib):
     assert b"null params" in lib.srn_last_error()
 
 
-# every (family, tile) pair a kernel exists for, per precision (the launchers' switches)
-KERNELS = {
-    "generic": {1, 2, 3, 4, 5}, "halo": {1, 2, 3, 4, 5}, "strip": {0},
-    ("f32", _lib.PREC_FP32): {5, 7, 9, 10, 11},
-    ("fast", _lib.PREC_FP32): {1, 2, 3, 4, 5, 7, 9}, ("fast", _lib.PREC_BF16X3): {1, 2, 3, 4, 5},
-    ("fast", _lib.PREC_BF16X6): {1, 2, 3, 4, 5, 7},
-}
+@functools.lru_cache(maxsize=None)
+def library_forms():
+    """the rows of srn_conv_gemm_forms: every kernel form the launchers' lists hold, in the library's order"""
+    from serenade_amd import build
+    build.build(verbose=False)  # no-op when up to date
+    return _lib.conv_forms()
+
+
+def form_rows(fam, p):
+    """the library's rows a launch of family `fam` is looked up in for p's arithmetic and B layout (the generic
+    family's fp32 rows run bf16x6 too)"""
+    prec = _lib.PREC_FP32 if fam == "generic" and p.precision == _lib.PREC_BF16X6 else p.precision
+    return [f for f in library_forms() if FAMILY[f.family] == fam and f.precision == prec and f.nmajor == p.w_nmajor]
+
+
+def forms_snapshot():
+    """what tests/conv_forms.json holds: the library's rows, and the names of the forms the sweep makes of them"""
+    from tests import _conv_cases
+    return {"fields": list(_lib.ConvForm._fields), "rows": [[FAMILY[f.family], *f[1:]] for f in library_forms()],
+            "sweep": list(_conv_cases.forms())}
+
+
+def test_library_forms_match_the_snapshot(lib):
+    """a row lost or added by accident changes the cases and the expectation of the sweep alike: the snapshot does not
+    move with it"""
+    want = json.load(open(FORMS_TABLE))
+    got = forms_snapshot()
+    assert got["fields"] == want["fields"]
+    assert got["rows"] == want["rows"], [r for r in got["rows"] + want["rows"] if (r in got["rows"]) != (r in want["rows"])]
 
 
 def sweep(n, seed=0):
@@ -205,13 +232,13 @@ def test_route_invariants_over_a_sweep(lib):
     for p in sweep(4000):
         fam, tile, ks = route(p)
         seen.add((fam, tile, ks > 1))
-        have = KERNELS.get(fam) or KERNELS[(fam, p.precision)]
-        assert tile in have, (key(p), p.precision, fam, tile)
+        rows = form_rows(fam, p)
+        assert tile in {f.tile for f in rows}, (key(p), p.precision, fam, tile)
         assert ks == 1 or (fam in ("f32", "fast") and p.ws and p.ws_bytes >= ks * p.n_batch * p.n_head * p.T_out * p.N * 4)
         assert fam not in ("halo", "strip") or p.precision == _lib.PREC_BF16X3
         assert fam != "f32" or p.precision == _lib.PREC_FP32
         if ks > 1:
-            assert tile == (11 if fam == "f32" else 4) and 2 <= ks <= 8
+            assert [tile] == [f.tile for f in rows if f.kslices] and 2 <= ks <= 8
         if ks > 1:  # the workspace query asks the same route
             assert lib.srn_conv_gemm_workspace_bytes(ctypes.byref(p)) == ks * p.n_batch * p.n_head * p.T_out * p.N * 4
     # the sweep reaches every family, the split-K slices of both and the single-stage / split-step tiles
@@ -251,4 +278,11 @@ def test_forced_routes_and_tiles(lib):
 
 
 if __name__ == "__main__":
-    print(json.dumps({f"{plan} {prec}": routes(plan, prec) for plan, prec in CONFIGS}, indent=1))
+    import sys
+    if sys.argv[1:] == ["forms"]:
+        snap = forms_snapshot()
+        lines = ",\n  ".join(json.dumps(r) for r in snap["rows"])
+        print('{\n "fields": %s,\n "rows": [\n  %s\n ],\n "sweep": %s\n}'
+              % (json.dumps(snap["fields"]), lines, json.dumps(snap["sweep"], indent=1).replace("\n", "\n ")))
+    else:
+        print(json.dumps({f"{plan} {prec}": routes(plan, prec) for plan, prec in CONFIGS}, indent=1))

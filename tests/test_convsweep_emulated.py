@@ -5,13 +5,14 @@ tolerance table cannot rot; every case's params, built as on a GPU (weight plane
 routed on the cross-compiled library and must reach the kernel form the case is meant for; and the forms reached are
 the forms that exist."""
 import ctypes
+import json
 
 import pytest
 import torch
 
 from serenade_amd import _lib, ops
 from tests import _conv_cases as C
-from tests.test_conv_route import FAMILY, device_params, lib  # noqa: F401  (lib is a fixture)
+from tests.test_conv_route import FAMILY, FORMS_TABLE, device_params, lib  # noqa: F401  (lib is a fixture)
 
 FORMS = list(C.forms())
 
@@ -69,9 +70,15 @@ def test_every_case_reaches_its_form(routed, form):
 
 
 def test_the_sweep_reaches_every_form_that_exists(routed):
-    """what the route answered over the whole sweep, against the forms the launchers' switches list"""
+    """what the route answered over the whole sweep, against the forms the library lists (srn_conv_gemm_forms)"""
     reached = {key for key, _ in routed.values()}
     assert reached == C.existing_forms(), reached ^ C.existing_forms()
+
+
+def test_the_sweep_has_its_60_forms():
+    """the forms the sweep makes of the library's list, by name and in order, against the committed snapshot"""
+    want = json.load(open(FORMS_TABLE))["sweep"]
+    assert len(FORMS) == 60 and FORMS == want, set(FORMS) ^ set(want)
 
 
 def test_tolerance_table_follows_its_rule():

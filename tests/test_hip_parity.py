@@ -15,6 +15,7 @@ from serenade_amd import _lib, models, ops, vocoder
 from serenade_amd.utils.synth import SERENADE_PARAMS, fill_state_dict, synth_inputs
 from tests import _emulator
 from tests._weights import hifigan_weights, serenade_weights, sub
+from tests.test_conv_route import library_forms
 
 import serenade_amd
 
@@ -129,7 +130,9 @@ def rnd(*s, seed=0):
     return torch.from_numpy(np.random.default_rng(seed).standard_normal(s).astype(np.float32))
 
 
-ALL_TILES = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11)  # 11: 64 x 64, loads two steps ahead; 7, 9: the single-LDS-stage forms (6, 8 run their twins 1, 2); 10: 32 x 64, step split over wave pairs
+# 0 (the route's own choice) and every id up to the last one the library lists a form for -- 11: 64 x 64, loads two steps
+# ahead; 7, 9: the single-LDS-stage forms (6, 8 have no form and run their twins 1, 2); 10: 32 x 64, step split over wave pairs
+ALL_TILES = tuple(range(max(f.tile for f in library_forms()) + 1))
 
 
 def test_library_exports_and_error_path(dev):
