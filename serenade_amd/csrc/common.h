@@ -58,10 +58,27 @@ __device__ __forceinline__ float srn_mish(float x) {
   return x > 20.0f ? x : y;  // branch-free select
 }
 
+// d/dx [x tanh(softplus(x))] = th + x (1 - th^2) sigmoid(x), th = tanh(softplus(x)) = n / (n + 2), n = e^x (e^x + 2)
+__device__ __forceinline__ float srn_mish_grad(float x) {
+  const float e = expf(fminf(x, 20.0f));
+  const float n = e * (e + 2.0f);
+  const float th = n / (n + 2.0f);
+  const float sg = 1.0f / (1.0f + expf(-x));
+  const float g = th + x * (1.0f - th * th) * sg;
+  return x > 20.0f ? 1.0f : g;
+}
+
 __device__ __forceinline__ float srn_silu(float x) { return x / (1.0f + expf(-x)); }
 
 __device__ __forceinline__ float srn_gelu_erf(float x) {
   return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
+}
+
+// d/dx gelu_erf(x) = Phi(x) + x phi(x)
+__device__ __forceinline__ float srn_gelu_grad(float x) {
+  const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
+  const float pdf = 0.39894228040143267794f * expf(-0.5f * x * x);
+  return cdf + x * pdf;
 }
 
 __device__ __forceinline__ float srn_act(float v, int act, float slope) {

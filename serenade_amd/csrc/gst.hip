@@ -3,38 +3,17 @@
 // layers are srn_conv_gemm launches, one per kernel row: models.StyleEncoder.build_ops.)  Reference: serenade/modules/gst/style_encoder.py:142-191,235-252 and
 // serenade/modules/gst/attention.py:110-184,298-300.
 #include "common.h"
+#include "row_common.h"
 
 namespace {
 
 // GRU recurrence on a PRECOMPUTED input projection gi = x W_ih^T + b_ih (one srn_conv_gemm over all (b, t) rows,
-// spread over the chip) -- the part that is inherently sequential is only h -> W_hh h, done here by one workgroup per
-// batch item with W_hh TRANSPOSED (w_hh_t [H][3H]) so that gate row tid reads consecutive addresses across lanes.
+// spread over the chip) -- the part that is inherently sequential is only h -> W_hh h, done by one workgroup per
+// batch item: row_common.h's gru_forward, which gst_train.hip's forward runs too (keeping every step).
 __global__ void gru_recur_last_kernel(const float* __restrict__ gi_all, const float* __restrict__ w_hh_t,
                                       const float* __restrict__ b_hh, float* __restrict__ hout, int T, int H) {
   extern __shared__ float sm[];  // h[H] | gh[3H]
-  float* sh = sm;
-  float* gh = sh + H;
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int G = 3 * H;
-  for (int i = tid; i < H; i += blockDim.x) sh[i] = 0.f;
-  __syncthreads();
-  for (int t = 0; t < T; ++t) {
-    if (tid < G) {
-      float c = 0.f;
-      for (int i = 0; i < H; ++i) c = fmaf(w_hh_t[(int64_t)i * G + tid], sh[i], c);
-      gh[tid] = c + b_hh[tid];
-    }
-    __syncthreads();
-    if (tid < H) {
-      const float* gi = gi_all + ((int64_t)b * T + t) * G;
-      const float r = 1.0f / (1.0f + expf(-(gi[tid] + gh[tid])));
-      const float z = 1.0f / (1.0f + expf(-(gi[H + tid] + gh[H + tid])));
-      const float n = tanhf(gi[2 * H + tid] + r * gh[2 * H + tid]);
-      sh[tid] = (1.0f - z) * n + z * sh[tid];
-    }
-    __syncthreads();
-  }
-  for (int i = tid; i < H; i += blockDim.x) hout[(int64_t)b * H + i] = sh[i];
+  gru_forward<false>(sm, gi_all, w_hh_t, b_hh, hout, nullptr, nullptr, T, H);
 }
 
 // Style-token attention on PRECOMPUTED keys / values: K = tanh(embs) W_k^T + b_k and V likewise do not depend on the
@@ -59,26 +38,7 @@ __global__ __launch_bounds__(256) void style_token_attention_kv_kernel(
     q[f] = a + bq[f];
   }
   __syncthreads();
-  const float inv = 1.0f / sqrtf((float)dk);
-  for (int idx = tid; idx < n_head * n_tok; idx += 256) {
-    const int h = idx / n_tok, t = idx - h * n_tok;
-    float a = 0.f;
-    for (int d = 0; d < dk; ++d) a = fmaf(q[h * dk + d], kk[t * F + h * dk + d], a);
-    sc[idx] = a * inv;
-  }
-  __syncthreads();
-  if (tid < n_head) {
-    float mx = -INFINITY;
-    for (int t = 0; t < n_tok; ++t) mx = fmaxf(mx, sc[tid * n_tok + t]);
-    float s = 0.f;
-    for (int t = 0; t < n_tok; ++t) {
-      const float e = expf(sc[tid * n_tok + t] - mx);
-      sc[tid * n_tok + t] = e;
-      s += e;
-    }
-    for (int t = 0; t < n_tok; ++t) sc[tid * n_tok + t] /= s;
-  }
-  __syncthreads();
+  token_scores_softmax(q, kk, sc, n_tok, F, n_head);
   for (int f = tid; f < F; f += 256) {
     const int h = f / dk;
     float a = 0.f;

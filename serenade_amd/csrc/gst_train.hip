@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "row_common.h"
 #include "serenade_hip.h"
 
 namespace {
@@ -207,39 +208,12 @@ __global__ __launch_bounds__(256) void col2im_s2_kernel(const float* __restrict_
 // ------------------------------------------------------------------------------------------------ GRU
 // forward on gi = x W_ih^T + b_ih (B, T, 3H): keeps h_0..h_T (hs (B, T+1, H)) and per step [r | z | n | W_hn h + b_hn]
 // (gates (B, T, 4H)).  One workgroup of 3H threads per item; w_hh_t (H, 3H) = W_hh transposed (coalesced matvec).
+// The recurrence is row_common.h's gru_forward, the one gst.hip's inference kernel runs.
 __global__ void gru_train_fwd_kernel(const float* __restrict__ gi_all, const float* __restrict__ w_hh_t,
                                      const float* __restrict__ b_hh, float* __restrict__ hs,
                                      float* __restrict__ gates, int T, int H) {
   extern __shared__ float sm_g[];  // h[H] | gh[3H]
-  float* sh = sm_g;
-  float* gh = sh + H;
-  const int b = blockIdx.x, tid = threadIdx.x, G = 3 * H;
-  for (int i = tid; i < H; i += blockDim.x) {
-    sh[i] = 0.f;
-    hs[(int64_t)b * (T + 1) * H + i] = 0.f;
-  }
-  __syncthreads();
-  for (int t = 0; t < T; ++t) {
-    if (tid < G) {
-      float c = 0.f;
-      for (int i = 0; i < H; ++i) c = fmaf(w_hh_t[(int64_t)i * G + tid], sh[i], c);
-      gh[tid] = c + b_hh[tid];
-    }
-    __syncthreads();
-    if (tid < H) {
-      const float* gi = gi_all + ((int64_t)b * T + t) * G;
-      float* gt = gates + ((int64_t)b * T + t) * 4 * H;
-      const float r = 1.0f / (1.0f + expf(-(gi[tid] + gh[tid])));
-      const float z = 1.0f / (1.0f + expf(-(gi[H + tid] + gh[H + tid])));
-      const float ghn = gh[2 * H + tid];
-      const float n = tanhf(gi[2 * H + tid] + r * ghn);
-      const float h = (1.0f - z) * n + z * sh[tid];
-      gt[tid] = r, gt[H + tid] = z, gt[2 * H + tid] = n, gt[3 * H + tid] = ghn;
-      sh[tid] = h;
-      hs[((int64_t)b * (T + 1) + t + 1) * H + tid] = h;
-    }
-    __syncthreads();
-  }
+  gru_forward<true>(sm_g, gi_all, w_hh_t, b_hh, nullptr, hs, gates, T, H);
 }
 
 // BPTT from the gradient of the last hidden state: dgi (B, T, 3H) (gradient of the input projection) and dgh (B, T, 3H)
@@ -293,26 +267,7 @@ __global__ __launch_bounds__(256) void token_attn_fwd_kernel(const float* __rest
   const int b = blockIdx.x, tid = threadIdx.x, dk = F / n_head;
   for (int i = tid; i < F; i += 256) sq[i] = q[(int64_t)b * F + i];
   __syncthreads();
-  const float scale = 1.0f / sqrtf((float)dk);
-  for (int i = tid; i < n_head * n_tok; i += 256) {
-    const int h = i / n_tok, t = i - h * n_tok;
-    float a = 0.f;
-    for (int d = 0; d < dk; ++d) a = fmaf(sq[h * dk + d], k[(int64_t)t * F + h * dk + d], a);
-    sc[i] = a * scale;
-  }
-  __syncthreads();
-  if (tid < n_head) {
-    float m = -3.0e38f;
-    for (int t = 0; t < n_tok; ++t) m = fmaxf(m, sc[tid * n_tok + t]);
-    float s = 0.f;
-    for (int t = 0; t < n_tok; ++t) {
-      const float e = expf(sc[tid * n_tok + t] - m);
-      sc[tid * n_tok + t] = e;
-      s += e;
-    }
-    for (int t = 0; t < n_tok; ++t) sc[tid * n_tok + t] /= s;
-  }
-  __syncthreads();
+  token_scores_softmax(sq, k, sc, n_tok, F, n_head);
   for (int i = tid; i < n_head * n_tok; i += 256) p[(int64_t)b * n_head * n_tok + i] = sc[i];
   for (int f = tid; f < F; f += 256) {
     const int h = f / dk;

@@ -2,44 +2,22 @@
 // the ResnetBlock1D tail (GroupNorm + Mish + residual + speaker-conditional LayerNorm), LayerNorm, masked
 // row softmax, and small layout / elementwise helpers.  All tensors are channels-last fp32; every kernel
 // moves 16 B per lane (float4) along the contiguous channel axis and reduces with wavefront shuffles.
+// The normalisation arithmetic itself (LayerNorm of a wave-owned row, the group statistics, GroupNorm + Mish) is
+// row_common.h's, shared with the training kernels of train.hip.
 #include "common.h"
 #include "conv_common.h"
+#include "row_common.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// GroupNorm statistics from the per-(32 rows x 32 cols) partials the conv epilogue wrote.
-// partials: [b][gn_mt][gn_nt][2];  out: mean[g], rstd[g] in LDS.  Called by all 256 threads.
+// GroupNorm statistics (row_common.h's gn_group_stats) -> mean[g], rstd[g] in LDS.  Called by all 256 threads.
 // n_rows: rows the statistics run over -- T (the reference's batched semantics: padded frames included), or the item's
 // own length when the producing conv zeroed its padded rows (exact ragged batches: the B = 1 result of every item).
 __device__ __forceinline__ void group_stats(const float* __restrict__ partials, int b, int T, int C, int groups,
                                             float eps, float* s_mean, float* s_rstd, int n_rows) {
-  const int gn_mt = (T + 31) / 32;
-  const int gn_nt = C / 32;
-  const int nt_per_g = (C / groups) / 32;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const float* base = partials + (int64_t)b * gn_mt * gn_nt * 2;
-  const int per_g = gn_mt * nt_per_g;
-  for (int g = wave; g < groups; g += 4) {
-    double s1 = 0.0, s2 = 0.0;
-    for (int e = lane; e < per_g; e += 64) {
-      const int mt = e / nt_per_g;
-      const int nt = g * nt_per_g + (e - mt * nt_per_g);
-      const float2 v = *reinterpret_cast<const float2*>(base + ((int64_t)mt * gn_nt + nt) * 2);
-      s1 += (double)v.x;
-      s2 += (double)v.y;
-    }
-    s1 = wave_sum_d(s1);
-    s2 = wave_sum_d(s2);
-    if (lane == 0) {
-      const double cnt = (double)max(n_rows, 1) * (double)(C / groups);
-      const double mean = s1 / cnt;
-      double var = s2 / cnt - mean * mean;
-      if (var < 0.0) var = 0.0;
-      s_mean[g] = (float)mean;
-      s_rstd[g] = (float)(1.0 / sqrt(var + (double)eps));
-    }
-  }
+  gn_group_stats(partials, b, T, C, groups, eps, n_rows,
+                 [&](int g, float mean, float rstd) { s_mean[g] = mean, s_rstd[g] = rstd; });
   __syncthreads();
 }
 
@@ -85,11 +63,7 @@ __global__ __launch_bounds__(256) void gn_mish_apply_kernel(const float* __restr
       const float4 ga = *reinterpret_cast<const float4*>(gamma + c);
       const float4 be = *reinterpret_cast<const float4*>(beta + c);
       const int g = c / cpg;
-      const float m = s_mean[g], rs = s_rstd[g];
-      o.x = srn_mish((v.x - m) * rs * ga.x + be.x);
-      o.y = srn_mish((v.y - m) * rs * ga.y + be.y);
-      o.z = srn_mish((v.z - m) * rs * ga.z + be.z);
-      o.w = srn_mish((v.w - m) * rs * ga.w + be.w);
+      o = gn_mish4(v, s_mean[g], s_rstd[g], ga, be);
       if (time_bias) {
         const float4 tb = *reinterpret_cast<const float4*>(time_bias + c);
         o.x += tb.x;
@@ -114,7 +88,6 @@ __global__ __launch_bounds__(256) void gn_mish_apply_kernel(const float* __restr
 // ------------------------------------------------------------------------------------------------
 // One wavefront per frame; C <= 1024 and C % 4 == 0 (up to MAXV float4 per lane).
 constexpr int TAIL_ROWS = 8;
-constexpr int MAXV = 4;
 
 __global__ __launch_bounds__(256) void resblock_tail_kernel(
     const float* __restrict__ c2, const float* __restrict__ partials, const float* __restrict__ gamma,
@@ -152,7 +125,6 @@ __global__ __launch_bounds__(256) void resblock_tail_kernel(
     const int64_t row = ((int64_t)b * T + r) * C;
     const bool valid = r < len;
     float4 v[MAXV];
-    float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
       const int c4 = lane + 64 * i;
@@ -162,79 +134,21 @@ __global__ __launch_bounds__(256) void resblock_tail_kernel(
         const float4 rr = rin[i];
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
         if (valid) {
-          const float4 x = xin[i];
           const float4 ga = *reinterpret_cast<const float4*>(gamma + c);
           const float4 be = *reinterpret_cast<const float4*>(beta + c);
           const int g = c / cpg;
-          const float m = s_mean[g], rs = s_rstd[g];
-          o.x = srn_mish((x.x - m) * rs * ga.x + be.x);
-          o.y = srn_mish((x.y - m) * rs * ga.y + be.y);
-          o.z = srn_mish((x.z - m) * rs * ga.z + be.z);
-          o.w = srn_mish((x.w - m) * rs * ga.w + be.w);
+          o = gn_mish4(xin[i], s_mean[g], s_rstd[g], ga, be);
         }
         v[i] = make_float4(o.x + rr.x, o.y + rr.y, o.z + rr.z, o.w + rr.w);
-        sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
       }
     }
-    const float mean = wave_sum(sum) * inv_c;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-      if (lane + 64 * i < c4n) {
-        const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
-        sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-      }
-    }
-    const float stdv = sqrtf(wave_sum(sq) * inv_c + ln_eps);
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-      const int c4 = lane + 64 * i;
-      if (c4 < c4n) {
-        const int c = c4 * 4;
-        const float4 sc = *reinterpret_cast<const float4*>(scale + (int64_t)b * ld_ss + c);
-        const float4 sh = *reinterpret_cast<const float4*>(shift + (int64_t)b * ld_ss + c);
-        float4 o;
-        o.x = (v[i].x - mean) / stdv * sc.x + sh.x;
-        o.y = (v[i].y - mean) / stdv * sc.y + sh.y;
-        o.z = (v[i].z - mean) / stdv * sc.z + sh.z;
-        o.w = (v[i].w - mean) / stdv * sc.w + sh.w;
-        *reinterpret_cast<float4*>(y + row + c) = o;
-        v[i] = o;
-      }
-    }
-    if (y2 != nullptr) {
-      // the transformer block's first LayerNorm (transformer.py:286) of the row just produced, from registers:
-      // layernorm_kernel's arithmetic, operation for operation
-      float sum2 = 0.f;
-#pragma unroll
-      for (int i = 0; i < MAXV; ++i)
-        if (lane + 64 * i < c4n) sum2 += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-      const float mean2 = wave_sum(sum2) * inv_c;
-      float sq2 = 0.f;
-#pragma unroll
-      for (int i = 0; i < MAXV; ++i) {
-        if (lane + 64 * i < c4n) {
-          const float dx = v[i].x - mean2, dy = v[i].y - mean2, dz = v[i].z - mean2, dw = v[i].w - mean2;
-          sq2 += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-        }
-      }
-      const float rstd2 = 1.0f / sqrtf(wave_sum(sq2) * inv_c + ln2_eps);
-#pragma unroll
-      for (int i = 0; i < MAXV; ++i) {
-        const int c4 = lane + 64 * i;
-        if (c4 < c4n) {
-          const int c = c4 * 4;
-          const float4 ga = *reinterpret_cast<const float4*>(ln2_gamma + c);
-          const float4 be = *reinterpret_cast<const float4*>(ln2_beta + c);
-          float4 o;
-          o.x = (v[i].x - mean2) * rstd2 * ga.x + be.x;
-          o.y = (v[i].y - mean2) * rstd2 * ga.y + be.y;
-          o.z = (v[i].z - mean2) * rstd2 * ga.z + be.z;
-          o.w = (v[i].w - mean2) * rstd2 * ga.w + be.w;
-          *reinterpret_cast<float4*>(y2 + row + c) = o;
-        }
-      }
-    }
+    // SpeakerAdapter (decoder.py:34-45): divides by the standard deviation
+    const float mean = row_sum(v, lane, c4n) * inv_c;
+    const float stdv = sqrtf(row_sqdev(v, mean, lane, c4n) * inv_c + ln_eps);
+    row_norm_affine_store<true>(v, mean, stdv, scale + (int64_t)b * ld_ss, shift + (int64_t)b * ld_ss, y + row, lane,
+                                c4n);
+    // the transformer block's first LayerNorm (transformer.py:286) of the row just produced, from registers
+    if (y2 != nullptr) row_layernorm_store(v, ln2_eps, ln2_gamma, ln2_beta, y2 + row, lane, c4n, inv_c);
   }
 }
 
@@ -246,43 +160,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   const int c4n = C / 4;
   const float inv_c = 1.0f / (float)C;
   for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < rows; r += (int64_t)gridDim.x * 4) {
-    const int64_t row = r * C;
     float4 v[MAXV];
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-      const int c4 = lane + 64 * i;
-      v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c4 < c4n) {
-        v[i] = *reinterpret_cast<const float4*>(x + row + c4 * 4);
-        sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-      }
-    }
-    const float mean = wave_sum(sum) * inv_c;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-      if (lane + 64 * i < c4n) {
-        const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
-        sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-      }
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(sq) * inv_c + eps);
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-      const int c4 = lane + 64 * i;
-      if (c4 < c4n) {
-        const int c = c4 * 4;
-        const float4 ga = *reinterpret_cast<const float4*>(gamma + c);
-        const float4 be = *reinterpret_cast<const float4*>(beta + c);
-        float4 o;
-        o.x = (v[i].x - mean) * rstd * ga.x + be.x;
-        o.y = (v[i].y - mean) * rstd * ga.y + be.y;
-        o.z = (v[i].z - mean) * rstd * ga.z + be.z;
-        o.w = (v[i].w - mean) * rstd * ga.w + be.w;
-        *reinterpret_cast<float4*>(y + row + c) = o;
-      }
-    }
+    row_load(x + r * C, v, lane, c4n);
+    row_layernorm_store(v, eps, gamma, beta, y + r * C, lane, c4n, inv_c);
   }
 }
 
@@ -536,35 +416,17 @@ extern "C" int srn_gn_mish_apply(const float* x, const float* gn_partials, const
   return 0;
 }
 
-extern "C" int srn_resblock_tail(const float* c2, const float* gn_partials, const float* gamma, const float* beta,
-                                 const int32_t* lens, const float* r, const float* scale, const float* shift,
-                                 int64_t ld_ss, float* y, int B, int T, int C, int groups, float gn_eps,
-                                 float ln_eps, int valid_stats, void* stream) {
-  SRN_CHECK_ARG(c2 && gn_partials && gamma && beta && r && scale && shift && y, "resblock_tail: null pointer");
-  SRN_CHECK_ARG(!valid_stats || lens, "resblock_tail: valid_stats needs lens");
-  SRN_CHECK_ARG(B > 0 && T > 0 && C > 0 && C % 4 == 0 && C <= 256 * MAXV, "resblock_tail: C=%d unsupported", C);
+// the two entry points of resblock_tail_kernel: name is the entry point's, for its error messages
+static int resblock_tail_launch(const char* name, const float* c2, const float* gn_partials, const float* gamma,
+                                const float* beta, const int32_t* lens, const float* r, const float* scale,
+                                const float* shift, int64_t ld_ss, float* y, int B, int T, int C, int groups, float gn_eps,
+                                float ln_eps, int valid_stats, const float* ln2_gamma, const float* ln2_beta, float* y2,
+                                float ln2_eps, void* stream) {
+  SRN_CHECK_ARG(c2 && gn_partials && gamma && beta && r && scale && shift && y, "%s: null pointer", name);
+  SRN_CHECK_ARG(!valid_stats || lens, "%s: valid_stats needs lens", name);
+  SRN_CHECK_ARG(B > 0 && T > 0 && C > 0 && C % 4 == 0 && C <= 256 * MAXV, "%s: C=%d unsupported", name, C);
   SRN_CHECK_ARG(groups > 0 && groups <= 64 && C % groups == 0 && (C / groups) % 32 == 0,
-                "resblock_tail: need (C / groups) %% 32 == 0");
-  const int rows_per_wg = (int64_t)B * ((T + TAIL_ROWS - 1) / TAIL_ROWS) < SMALL_GRID ? TAIL_ROWS / 2 : TAIL_ROWS;
-  dim3 grid((T + rows_per_wg - 1) / rows_per_wg, B);
-  hipLaunchKernelGGL(resblock_tail_kernel, grid, dim3(256), 0, (hipStream_t)stream, c2, gn_partials, gamma, beta,
-                     lens, r, scale, shift, ld_ss, y, T, C, groups, gn_eps, ln_eps, valid_stats, nullptr, nullptr,
-                     nullptr, 0.f, rows_per_wg);
-  SRN_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int srn_resblock_tail_ln(const float* c2, const float* gn_partials, const float* gamma, const float* beta,
-                                    const int32_t* lens, const float* r, const float* scale, const float* shift,
-                                    int64_t ld_ss, float* y, int B, int T, int C, int groups, float gn_eps,
-                                    float ln_eps, int valid_stats, const float* ln2_gamma, const float* ln2_beta,
-                                    float* y2, float ln2_eps, void* stream) {
-  SRN_CHECK_ARG(c2 && gn_partials && gamma && beta && r && scale && shift && y && ln2_gamma && ln2_beta && y2,
-                "resblock_tail_ln: null pointer");
-  SRN_CHECK_ARG(!valid_stats || lens, "resblock_tail_ln: valid_stats needs lens");
-  SRN_CHECK_ARG(B > 0 && T > 0 && C > 0 && C % 4 == 0 && C <= 256 * MAXV, "resblock_tail_ln: C=%d unsupported", C);
-  SRN_CHECK_ARG(groups > 0 && groups <= 64 && C % groups == 0 && (C / groups) % 32 == 0,
-                "resblock_tail_ln: need (C / groups) %% 32 == 0");
+                "%s: need (C / groups) %% 32 == 0", name);
   const int rows_per_wg = (int64_t)B * ((T + TAIL_ROWS - 1) / TAIL_ROWS) < SMALL_GRID ? TAIL_ROWS / 2 : TAIL_ROWS;
   dim3 grid((T + rows_per_wg - 1) / rows_per_wg, B);
   hipLaunchKernelGGL(resblock_tail_kernel, grid, dim3(256), 0, (hipStream_t)stream, c2, gn_partials, gamma, beta,
@@ -572,6 +434,24 @@ extern "C" int srn_resblock_tail_ln(const float* c2, const float* gn_partials, c
                      y2, ln2_eps, rows_per_wg);
   SRN_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int srn_resblock_tail(const float* c2, const float* gn_partials, const float* gamma, const float* beta,
+                                 const int32_t* lens, const float* r, const float* scale, const float* shift,
+                                 int64_t ld_ss, float* y, int B, int T, int C, int groups, float gn_eps,
+                                 float ln_eps, int valid_stats, void* stream) {
+  return resblock_tail_launch("resblock_tail", c2, gn_partials, gamma, beta, lens, r, scale, shift, ld_ss, y, B, T, C,
+                              groups, gn_eps, ln_eps, valid_stats, nullptr, nullptr, nullptr, 0.f, stream);
+}
+
+extern "C" int srn_resblock_tail_ln(const float* c2, const float* gn_partials, const float* gamma, const float* beta,
+                                    const int32_t* lens, const float* r, const float* scale, const float* shift,
+                                    int64_t ld_ss, float* y, int B, int T, int C, int groups, float gn_eps,
+                                    float ln_eps, int valid_stats, const float* ln2_gamma, const float* ln2_beta,
+                                    float* y2, float ln2_eps, void* stream) {
+  SRN_CHECK_ARG(ln2_gamma && ln2_beta && y2, "resblock_tail_ln: null pointer");
+  return resblock_tail_launch("resblock_tail_ln", c2, gn_partials, gamma, beta, lens, r, scale, shift, ld_ss, y, B, T,
+                              C, groups, gn_eps, ln_eps, valid_stats, ln2_gamma, ln2_beta, y2, ln2_eps, stream);
 }
 
 extern "C" int srn_layernorm(const float* x, const float* gamma, const float* beta, float* y, int64_t rows, int C,

@@ -13,34 +13,19 @@
 //   srn_adamw                       torch.optim.AdamW step on one flat fp32 buffer, gradient scale (clip) folded in
 // Column sums (d gamma, d beta, per-batch adapter gradients) leave as per-row-chunk partial sums [..][chunk][2][C];
 // the host adds the few chunks (no atomics: results are bit-reproducible).
+// The forward arithmetic these differentiate (row LayerNorm, group statistics, GroupNorm + Mish) and the AdamW update are
+// row_common.h's: the forward kernels of norm_act.hip and the two optimizer entry points run the same statements.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "row_common.h"
 #include "serenade_hip.h"
 
 namespace {
 
-constexpr int MAXV = 4;       // float4 per lane: C <= 1024
 constexpr int LN_ROWS = 8;    // rows per workgroup of the row-LayerNorm backward (one chunk of partial sums): 32 left a
                               // B = 4 x L = 1024 step with 128 workgroups on 256 CUs (24 us per launch)
 constexpr int GN_ROWS = 8;    // rows per workgroup of the GroupNorm backward reduction (same reason)
-
-// d/dx [x tanh(softplus(x))] = th + x (1 - th^2) sigmoid(x), th = tanh(softplus(x)) = n / (n + 2), n = e^x (e^x + 2)
-__device__ __forceinline__ float mish_grad(float x) {
-  const float e = expf(fminf(x, 20.0f));
-  const float n = e * (e + 2.0f);
-  const float th = n / (n + 2.0f);
-  const float sg = 1.0f / (1.0f + expf(-x));
-  const float g = th + x * (1.0f - th * th) * sg;
-  return x > 20.0f ? 1.0f : g;
-}
-
-// d/dx gelu_erf(x) = Phi(x) + x phi(x)
-__device__ __forceinline__ float gelu_grad(float x) {
-  const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
-  const float pdf = 0.39894228040143267794f * expf(-0.5f * x * x);
-  return cdf + x * pdf;
-}
 
 // ---- per-frame LayerNorm with per-(batch, channel) multiplier m and offset a: y = xhat * m[b] + a[b]
 __global__ __launch_bounds__(256) void rowln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ m,
@@ -55,41 +40,8 @@ __global__ __launch_bounds__(256) void rowln_fwd_kernel(const float* __restrict_
   for (int t = blockIdx.x * 4 + wave; t < T; t += gridDim.x * 4) {
     const int64_t row = ((int64_t)b * T + t) * C;
     float4 v[MAXV];
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-      const int c4 = lane + 64 * i;
-      v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c4 < c4n) {
-        v[i] = *reinterpret_cast<const float4*>(x + row + c4 * 4);
-        sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-      }
-    }
-    const float mean = wave_sum(sum) * inv_c;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-      if (lane + 64 * i < c4n) {
-        const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
-        sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-      }
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(sq) * inv_c + eps);
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-      const int c4 = lane + 64 * i;
-      if (c4 < c4n) {
-        const int c = c4 * 4;
-        const float4 mm = *reinterpret_cast<const float4*>(m + c);
-        const float4 aa = *reinterpret_cast<const float4*>(a + c);
-        float4 o;
-        o.x = (v[i].x - mean) * rstd * mm.x + aa.x;
-        o.y = (v[i].y - mean) * rstd * mm.y + aa.y;
-        o.z = (v[i].z - mean) * rstd * mm.z + aa.z;
-        o.w = (v[i].w - mean) * rstd * mm.w + aa.w;
-        *reinterpret_cast<float4*>(y + row + c) = o;
-      }
-    }
+    row_load(x + row, v, lane, c4n);
+    row_layernorm_store(v, eps, m, a, y + row, lane, c4n, inv_c);
   }
 }
 
@@ -112,27 +64,10 @@ __global__ __launch_bounds__(256) void rowln_bwd_kernel(const float* __restrict_
   for (int t = chunk * LN_ROWS + wave; t < t_end; t += 4) {
     const int64_t row = ((int64_t)b * T + t) * C;
     float4 v[MAXV], g[MAXV];
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-      const int c4 = lane + 64 * i;
-      v[i] = g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c4 < c4n) {
-        v[i] = *reinterpret_cast<const float4*>(x + row + c4 * 4);
-        g[i] = *reinterpret_cast<const float4*>(dy + row + c4 * 4);
-        sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-      }
-    }
-    const float mean = wave_sum(sum) * inv_c;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-      if (lane + 64 * i < c4n) {
-        const float dx0 = v[i].x - mean, dx1 = v[i].y - mean, dx2 = v[i].z - mean, dx3 = v[i].w - mean;
-        sq += (dx0 * dx0 + dx1 * dx1) + (dx2 * dx2 + dx3 * dx3);
-      }
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(sq) * inv_c + eps);
+    row_load(x + row, v, lane, c4n);
+    row_load(dy + row, g, lane, c4n);
+    const float mean = row_sum(v, lane, c4n) * inv_c;
+    const float rstd = 1.0f / sqrtf(row_sqdev(v, mean, lane, c4n) * inv_c + eps);
     float s1 = 0.f, s2 = 0.f;
     float4 gh[MAXV];
 #pragma unroll
@@ -141,12 +76,11 @@ __global__ __launch_bounds__(256) void rowln_bwd_kernel(const float* __restrict_
       gh[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (c4 < c4n) {
         const float4 mm = *reinterpret_cast<const float4*>(m + c4 * 4);
-        v[i].x = (v[i].x - mean) * rstd, v[i].y = (v[i].y - mean) * rstd;  // xhat
-        v[i].z = (v[i].z - mean) * rstd, v[i].w = (v[i].w - mean) * rstd;
+        v[i] = xhat4(v[i], mean, rstd);
         am[i].x += g[i].x * v[i].x, am[i].y += g[i].y * v[i].y, am[i].z += g[i].z * v[i].z, am[i].w += g[i].w * v[i].w;
         aa[i].x += g[i].x, aa[i].y += g[i].y, aa[i].z += g[i].z, aa[i].w += g[i].w;
-        gh[i].x = g[i].x * mm.x, gh[i].y = g[i].y * mm.y, gh[i].z = g[i].z * mm.z, gh[i].w = g[i].w * mm.w;
-        s1 += (gh[i].x + gh[i].y) + (gh[i].z + gh[i].w);
+        gh[i] = mul4(g[i], mm);
+        s1 += hsum4(gh[i]);
         s2 += (gh[i].x * v[i].x + gh[i].y * v[i].y) + (gh[i].z * v[i].z + gh[i].w * v[i].w);
       }
     }
@@ -207,12 +141,8 @@ __global__ __launch_bounds__(256) void gn_mish_bwd_partial_kernel(
       const int64_t at = ((int64_t)b * T + t) * C + c;
       const float4 hv = *reinterpret_cast<const float4*>(h + at);
       const float4 gv = *reinterpret_cast<const float4*>(dy + at);
-      float4 xh, dg;
-      xh.x = (hv.x - mu) * rs, xh.y = (hv.y - mu) * rs, xh.z = (hv.z - mu) * rs, xh.w = (hv.w - mu) * rs;
-      dg.x = gv.x * mish_grad(xh.x * ga.x + be.x);
-      dg.y = gv.y * mish_grad(xh.y * ga.y + be.y);
-      dg.z = gv.z * mish_grad(xh.z * ga.z + be.z);
-      dg.w = gv.w * mish_grad(xh.w * ga.w + be.w);
+      const float4 xh = xhat4(hv, mu, rs);
+      const float4 dg = gn_mish_dg4(gv, xh, ga, be);
       a0.x += dg.x, a0.y += dg.y, a0.z += dg.z, a0.w += dg.w;
       a1.x += dg.x * xh.x, a1.y += dg.y * xh.y, a1.z += dg.z * xh.z, a1.w += dg.w * xh.w;
     }
@@ -250,16 +180,13 @@ __global__ __launch_bounds__(256) void gn_mish_bwd_apply_kernel(
     const float A = gsum[(b * groups + g) * 2] * inv_n, Bq = gsum[(b * groups + g) * 2 + 1] * inv_n;
     const int64_t at = ((int64_t)b * T + t) * C + c;
     const float4 hv = *reinterpret_cast<const float4*>(h + at);
-    float4 xh, dg = make_float4(0.f, 0.f, 0.f, 0.f);
-    xh.x = (hv.x - mu) * rs, xh.y = (hv.y - mu) * rs, xh.z = (hv.z - mu) * rs, xh.w = (hv.w - mu) * rs;
+    const float4 xh = xhat4(hv, mu, rs);
+    float4 dg = make_float4(0.f, 0.f, 0.f, 0.f);
     if (t < len) {
       const float4 ga = *reinterpret_cast<const float4*>(gamma + c);
       const float4 be = *reinterpret_cast<const float4*>(beta + c);
       const float4 gv = *reinterpret_cast<const float4*>(dy + at);
-      dg.x = gv.x * mish_grad(xh.x * ga.x + be.x) * ga.x;
-      dg.y = gv.y * mish_grad(xh.y * ga.y + be.y) * ga.y;
-      dg.z = gv.z * mish_grad(xh.z * ga.z + be.z) * ga.z;
-      dg.w = gv.w * mish_grad(xh.w * ga.w + be.w) * ga.w;
+      dg = mul4(gn_mish_dg4(gv, xh, ga, be), ga);
     }
     float4 o;
     o.x = rs * (dg.x - A - xh.x * Bq);
@@ -270,35 +197,13 @@ __global__ __launch_bounds__(256) void gn_mish_bwd_apply_kernel(
   }
 }
 
-// ---- GroupNorm statistics from the conv epilogue's 32 x 32 tile sums: (mean, rstd)[b][g], fp64 accumulation,
-// statistics over the padded length T (the arithmetic of norm_act.hip's group_stats, kept for the backward pass)
+// ---- GroupNorm statistics from the conv epilogue's 32 x 32 tile sums: (mean, rstd)[b][g] over the padded length T,
+// kept for the backward pass: row_common.h's gn_group_stats, which the forward kernels of norm_act.hip run as well
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ partials, float* __restrict__ mean,
                                                        float* __restrict__ rstd, int T, int C, int groups, float eps) {
   const int b = blockIdx.x;
-  const int gn_mt = (T + 31) / 32, gn_nt = C / 32, nt_per_g = (C / groups) / 32;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const float* base = partials + (int64_t)b * gn_mt * gn_nt * 2;
-  const int per_g = gn_mt * nt_per_g;
-  for (int g = wave; g < groups; g += 4) {
-    double s1 = 0.0, s2 = 0.0;
-    for (int e = lane; e < per_g; e += 64) {
-      const int mt = e / nt_per_g;
-      const int nt = g * nt_per_g + (e - mt * nt_per_g);
-      const float2 v = *reinterpret_cast<const float2*>(base + ((int64_t)mt * gn_nt + nt) * 2);
-      s1 += (double)v.x;
-      s2 += (double)v.y;
-    }
-    s1 = wave_sum_d(s1);
-    s2 = wave_sum_d(s2);
-    if (lane == 0) {
-      const double cnt = (double)T * (double)(C / groups);
-      const double m = s1 / cnt;
-      double var = s2 / cnt - m * m;
-      if (var < 0.0) var = 0.0;
-      mean[b * groups + g] = (float)m;
-      rstd[b * groups + g] = (float)(1.0 / sqrt(var + (double)eps));
-    }
-  }
+  gn_group_stats(partials, b, T, C, groups, eps, T,
+                 [&](int g, float m, float rs) { mean[b * groups + g] = m, rstd[b * groups + g] = rs; });
 }
 
 // ---- column sums of per-chunk partial sums: col[b][i] = sum_chunk partial[b][chunk][i], i < n_out (= 2 C for the
@@ -412,28 +317,19 @@ __global__ __launch_bounds__(256) void geglu_bwd_kernel(const float* __restrict_
     float4 dh, dg;
     dh.x = d.x * srn_gelu_erf(g.x), dh.y = d.y * srn_gelu_erf(g.y);
     dh.z = d.z * srn_gelu_erf(g.z), dh.w = d.w * srn_gelu_erf(g.w);
-    dg.x = d.x * h.x * gelu_grad(g.x), dg.y = d.y * h.y * gelu_grad(g.y);
-    dg.z = d.z * h.z * gelu_grad(g.z), dg.w = d.w * h.w * gelu_grad(g.w);
+    dg.x = d.x * h.x * srn_gelu_grad(g.x), dg.y = d.y * h.y * srn_gelu_grad(g.y);
+    dg.z = d.z * h.z * srn_gelu_grad(g.z), dg.w = d.w * h.w * srn_gelu_grad(g.w);
     *reinterpret_cast<float4*>(dhg + r * 2 * inner + c) = dh;
     *reinterpret_cast<float4*>(dhg + r * 2 * inner + inner + c) = dg;
   }
 }
 
-// ---- torch.optim.AdamW (decoupled weight decay) on a flat buffer; g is multiplied by gscale first (gradient clipping)
+// ---- torch.optim.AdamW on a flat buffer (row_common.h's adamw_update)
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
                                                     float beta1, float beta2, float eps, float wd, float bc1, float bc2,
                                                     float gscale) {
-  const float step = lr / bc1;
-  const float inv_sqrt_bc2 = 1.0f / sqrtf(bc2);
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float gi = g[i] * gscale;
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-    const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
-    pi -= step * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
-    p[i] = pi, m[i] = mi, v[i] = vi;
-  }
+  adamw_update(p, g, m, v, n, lr, beta1, beta2, eps, wd, bc1, bc2, gscale);
 }
 
 // the same update with its step-dependent scalars read from device memory (dyn = {lr, bc1, bc2, grad_scale}): the
@@ -442,17 +338,7 @@ __global__ __launch_bounds__(256) void adamw_dyn_kernel(float* __restrict__ p, c
                                                         float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                         float beta1, float beta2, float eps, float wd,
                                                         const float* __restrict__ dyn) {
-  const float lr = dyn[0], bc1 = dyn[1], bc2 = dyn[2], gscale = dyn[3];
-  const float step = lr / bc1;
-  const float inv_sqrt_bc2 = 1.0f / sqrtf(bc2);
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float gi = g[i] * gscale;
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-    const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
-    pi -= step * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
-    p[i] = pi, m[i] = mi, v[i] = vi;
-  }
+  adamw_update(p, g, m, v, n, dyn[0], beta1, beta2, eps, wd, dyn[1], dyn[2], dyn[3]);
 }
 
 // sum of squares in fp64: partial[block] for <= 1024 blocks (the host adds them): clip_grad_norm_'s total norm

@@ -322,6 +322,56 @@ def _partials(x):
     return torch.stack([t.sum(dim=(2, 4)), (t ** 2).sum(dim=(2, 4))], dim=-1).contiguous()
 
 
+def _fused_tail_equals_tail_then_layernorm(dev, x, lens, gam, bet, res, ss, g2, b2, groups):
+    """srn_resblock_tail_ln against srn_resblock_tail + srn_layernorm, bit for bit (both run row_common.h's LayerNorm)"""
+    B, Tn, C = x.shape
+    d = lambda t: t.to(dev)
+    args = (d(x), d(_partials(x)), d(gam), d(bet), d(lens), d(res), (d(ss), C), (d(ss), 2 * C), 4 * C)
+    y_a, y_b, n_a, n_b = (torch.zeros(B, Tn, C, device=dev) for _ in range(4))
+    ops.resblock_tail_op(*args, y_a, B, Tn, C, groups=groups)()
+    ops.layernorm_op(y_a, d(g2), d(b2), n_a, B * Tn, C)()
+    ops.resblock_tail_ln_op(*args, y_b, d(g2), d(b2), n_b, B, Tn, C, groups=groups)()
+    torch.cuda.synchronize()
+    assert y_a.abs().sum() > 0 and n_a.abs().sum() > 0
+    assert torch.equal(y_a, y_b) and torch.equal(n_a, n_b)
+
+
+@pytest.mark.parametrize("C,groups", [(128, 4), (320, 2), (1024, 8)])
+def test_fused_tail_is_bit_identical_to_tail_then_layernorm(dev, C, groups):
+    """half a wave; a partly filled second float4 slot; every slot full.  B = 2, T = 5: the last rows' waves idle"""
+    B, Tn = 2, 5
+    x = rnd(B, Tn, C, seed=33) * 2 + 0.3
+    lens = torch.tensor([5, 3], dtype=torch.int32)
+    _fused_tail_equals_tail_then_layernorm(dev, x, lens, 1 + 0.1 * rnd(C, seed=34), 0.1 * rnd(C, seed=35),
+                                           rnd(B, Tn, C, seed=38), rnd(B, 4 * C, seed=37), 1 + 0.1 * rnd(C, seed=45),
+                                           0.1 * rnd(C, seed=46), groups)
+
+
+@pytest.mark.parametrize("C", [4, 260, 1024])
+def test_rowln_fwd_with_a_shared_affine_is_bit_identical_to_layernorm(dev, C):
+    """one lane; lane 0 alone in the second float4 slot; every slot full.  10 rows: the last workgroup is partly empty"""
+    B, Tn = 2, 5
+    x = (rnd(B, Tn, C, seed=50) * 2 + 0.3).to(dev)
+    m, a = (1 + 0.1 * rnd(C, seed=51)).to(dev), (0.1 * rnd(C, seed=52)).to(dev)
+    y_a, y_b = torch.zeros(B, Tn, C, device=dev), torch.zeros(B, Tn, C, device=dev)
+    ops.CallOp("srn_rowln_fwd", (x, m, 0, a, 0, y_a, B, Tn, C, 1e-5))()
+    ops.layernorm_op(x, m, a, y_b, B * Tn, C)()
+    torch.cuda.synchronize()
+    assert y_a.abs().sum() > 0 and torch.equal(y_a, y_b)
+
+
+@pytest.mark.parametrize("H", [4, 128, 1024 // 3])  # both launchers require 3 H <= 1024
+def test_gru_recur_last_is_the_last_state_of_gru_train_fwd(dev, H):
+    B, Tn = 3, 5
+    gi, w, bh = rnd(B, Tn, 3 * H, seed=70).to(dev), (rnd(H, 3 * H, seed=71) / 11).to(dev), (0.1 * rnd(3 * H, seed=72)).to(dev)
+    h = torch.zeros(B, H, device=dev)
+    hs, gates = torch.zeros(B, Tn + 1, H, device=dev), torch.zeros(B, Tn, 4 * H, device=dev)
+    ops.gru_recur_last_op(gi, w, bh, h, B, Tn, H)()
+    ops.CallOp("srn_gru_train_fwd", (gi, w, bh, hs, gates, B, Tn, H))()
+    torch.cuda.synchronize()
+    assert h.abs().sum() > 0 and torch.equal(h, hs[:, Tn])
+
+
 def test_norm_and_elementwise_kernels(dev):
     B, Tn, C = 2, 75, 512
     x = rnd(B, Tn, C, seed=33) * 2 + 0.3
@@ -363,14 +413,7 @@ def test_norm_and_elementwise_kernels(dev):
                                                 (ss, 2 * C), 4 * C, torch.zeros(B, Tn, C), B, Tn, C, 8, 1e-5, 1e-5, 0,
                                                 g2, b2, torch.zeros(B, Tn, C), 1e-5])
     assert e < KTOL.k
-    d = lambda t: t.to(dev)
-    args = (d(x), d(_partials(x)), d(gam), d(bet), d(lens), d(rnd(B, Tn, C, seed=38)), (d(ss), C), (d(ss), 2 * C), 4 * C)
-    y_a, y_b, n_a, n_b = (torch.zeros(B, Tn, C, device=dev) for _ in range(4))
-    ops.resblock_tail_op(*args[:8], args[8], y_a, B, Tn, C)()
-    ops.layernorm_op(y_a, d(g2), d(b2), n_a, B * Tn, C)()
-    ops.resblock_tail_ln_op(*args[:8], args[8], y_b, d(g2), d(b2), n_b, B, Tn, C)()
-    torch.cuda.synchronize()
-    assert torch.equal(y_a, y_b) and torch.equal(n_a, n_b)
+    _fused_tail_equals_tail_then_layernorm(dev, x, lens, gam, bet, rnd(B, Tn, C, seed=38), ss, g2, b2, 8)
     src = rnd(2, 9, 5, seed=44)
     e = _run_call(dev, "srn_scatter_rows", [src, 45, 5, torch.zeros(2, 16, 8), 128, 8, 2,
                                             torch.tensor([3, 7], dtype=torch.int32),

@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import serenade_oracle as O
-from serenade_amd import _lib, training
+from serenade_amd import _lib, ops, training
 from tests._weights import serenade_weights, sub
 from tests.test_training_emulated import _case, _golden_case, _oracle_grads, check_against_reference_gradients, rel
 
@@ -100,6 +100,24 @@ def test_row_layernorm_backward(dev):
         y.backward(dy.to(dev))
         for u, r in ((xd, xr), (md, mr), (ad, ar)):
             assert rel(u.grad.cpu(), r.grad) < 2e-5, per_b
+
+
+@pytest.mark.parametrize("n", [1, 255, 769])
+def test_adamw_and_adamw_dyn_are_the_same_update(dev, n):
+    """the eager and the captured step's optimizer, bit for bit: at step 1 the bias corrections are 1 - beta, no powf"""
+    g = torch.Generator().manual_seed(11)
+    lr, b1, b2, eps, wd, scale = 1e-3, 0.9, 0.98, 1e-8, 0.01, 0.5
+    init = [torch.randn(n, generator=g), torch.randn(n, generator=g), 0.1 * torch.randn(n, generator=g),
+            0.1 * torch.rand(n, generator=g)]
+    p_a, gr, m_a, v_a = (t.to(dev) for t in init)
+    p_b, _, m_b, v_b = (t.to(dev) for t in init)
+    f = np.float32
+    dyn = torch.tensor(np.array([f(lr), f(1) - f(b1), f(1) - f(b2), f(scale)], dtype=np.float32)).to(dev)
+    ops.CallOp("srn_adamw", (p_a, gr, m_a, v_a, n, lr, b1, b2, eps, wd, 1, scale))()
+    ops.CallOp("srn_adamw_dyn", (p_b, gr, m_b, v_b, n, b1, b2, eps, wd, dyn))()
+    torch.cuda.synchronize()
+    assert not torch.equal(p_a.cpu(), init[0])
+    assert torch.equal(p_a, p_b) and torch.equal(m_a, m_b) and torch.equal(v_a, v_b)
 
 
 def test_attention_core_backward(dev):
