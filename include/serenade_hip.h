@@ -740,6 +740,33 @@ int srn_trim_bounds(const void* x, int x_is_f64, int64_t x_bs, const int32_t* le
 int srn_wave_window(const void* x, int x_is_f64, int64_t x_bs, const int32_t* starts, const int32_t* counts, int pad,
                     void* y, int64_t y_bs, int B, int width, void* stream);
 
+/*
+ * Stage 2 of the recipe and the batch the training step eats (serenade_amd/stats.py drives both, tests/_stats_ref.py is
+ * the restatement): the per-utterance sums behind sklearn's StandardScaler / MinMaxScaler.partial_fit of
+ * serenade/bin/compute_statistics.py:121-144, and FeatsDataset's normalisation (serenade/datasets/
+ * audio_mel_dataset.py:96-110) followed by SSCCollater's sort, drop and zero padding (serenade/collaters/ssc.py:50-77).
+ * Input is PACKED: x (R, C) float32 row-major, the rows of all B items one after another; row_off [B + 1] int64 on the
+ * device, item b the rows [row_off[b], row_off[b + 1]).  Nothing outside an item is read (offsets are clamped to
+ * [0, R]).  Every sum is fp64, contraction off, in an order that depends on the item's row count alone, so a batched
+ * call is bit for bit its B = 1 calls.
+ */
+#define SRN_STATS_COL_TILE 64 /* columns per workgroup of srn_col_moments */
+/* compute_statistics.py:138-141 -> what one partial_fit needs of one utterance.  Per item b and column c, with
+ * n = the item's rows: sum (B, C) float64 = sum_r x; m2 (B, C) float64 = sum_r d^2 - (sum_r d)^2 / n with
+ * d = (double)x - sum / n (sklearn.utils.extmath._incremental_mean_and_var's new_unnormalized_variance); mn / mx (B, C)
+ * float32, the input's own values; nonfinite (B) int32, the item's count of NaN / +-inf (zeroed here by a kernel).
+ * Order of every sum: wave w = 0 .. 3 adds the rows w, w + 4, ... in turn, then (s0 + s1) + s2 + s3. */
+int srn_col_moments(const float* x, const int64_t* row_off, int64_t R, double* sum, double* m2, float* mn, float* mx,
+                    int32_t* nonfinite, int B, int C, void* stream);
+/* audio_mel_dataset.py:96-110 + collaters/ssc.py:50-77 for one track: out (Bout, Tmax, C) float32,
+ * out[b][t][c] = (x[row_off[order[b]] + t][c] - sub[c]) / div[c] for t < the item's rows, exact +0.0 for the rest up
+ * to Tmax; every element of out is written.  order (Bout) int32 on the device picks and sorts the items (an index
+ * outside [0, B) reads as an empty item).  wide 1: sub / div (C) float64, both operations fp64, one rounding to
+ * float32 (numpy's float32 - float64, / float64, then .float()); wide 0: sub / div (C) float32, both operations
+ * float32 (numpy's float32 track against MinMaxScaler's float32 data_min_ / span).  Tmax C < 2^31. */
+int srn_scale_collate(const float* x, const int64_t* row_off, int64_t R, const int32_t* order, const void* sub,
+                      const void* div, int wide, float* out, int Tmax, int B, int Bout, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,8 @@ _SIGS = {
     "srn_resample": (c_int, [_P, c_int, c_int64, _P, _P, _P, _P, c_int64] + [c_int] * 7 + [_P]),
     "srn_trim_bounds": (c_int, [_P, c_int, c_int64, _P, _P, _P] + [c_int] * 5 + [c_double, _P]),
     "srn_wave_window": (c_int, [_P, c_int, c_int64, _P, _P, c_int, _P, c_int64, c_int, c_int, _P]),
+    "srn_col_moments": (c_int, [_P, _P, c_int64] + [_P] * 5 + [c_int, c_int, _P]),
+    "srn_scale_collate": (c_int, [_P, _P, c_int64, _P, _P, _P, c_int, _P] + [c_int] * 4 + [_P]),
 }
 
 EXPORTS = tuple(_SIGS)
