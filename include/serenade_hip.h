@@ -252,8 +252,9 @@ int srn_out_conv_tanh(const float* x, const float* w, const float* bias, float* 
  * intermediate `xt` never leaves LDS, weights stream through a double-buffered LDS stage -- one HBM read and one
  * write per unit instead of five passes.  Optionally the stage bookkeeping of HiFiGANGenerator.forward
  * (hifigan.py:183-186) rides in the epilogue:  y = (y + res2) / post_div.
- *   x, out, res2: (n_batch, T, C) channels-last fp32, rows contiguous (ld = C); out must not alias x (res2 may be
- *   out: in-place running sum).
+ *   x, out, res2: (n_batch, T, C) channels-last fp32, rows contiguous (ld = C), items x_bs / out_bs / res2_bs apart;
+ *   out must not alias x (res2 may be out: in-place running sum).  x: 16-byte aligned, x_bs % 4 == 0; out and res2 need
+ *   no more than a float's alignment.
  *   w1, w2: packed [C][k * C] fp32 (tap-major, as srn_conv_gemm's k-major weights); b1, b2: (C).
  *   w1_hi, w2_hi: SRN_PREC_BF16X3 only -- the same weights as bf16 planes [C][k][C / 32][hi 32 | lo 32].
  */
@@ -272,7 +273,15 @@ typedef struct SrnResUnitParams {
 } SrnResUnitParams;
 enum { SRN_RESUNIT_ROUTE_SHARED = 1 };
 
+
 int srn_hifigan_resunit(const SrnResUnitParams* p, void* stream);
+/* The implementation srn_hifigan_resunit runs for these params, from the very code its launch runs (pure host code, no
+ * launch): out[0] = form (SRN_RESUNIT_FORM_*), out[1] = output tiles per batch item, out[2] = workgroups launched
+ * (each walks the tiles of the whole batch, out[2] apart).  Returns the launch's validation error where the launch would.
+ * Exact fp32 (and SRN_PREC_BF16X6, which runs it) takes resunit_f32.hip's form unless the route asks for the shared one,
+ * slope lies outside [0, 1] or one item reaches 2^31 bytes. */
+enum { SRN_RESUNIT_FORM_F32 = 0, SRN_RESUNIT_FORM_SHARED_F32 = 1, SRN_RESUNIT_FORM_BF16X3 = 2 };
+int srn_hifigan_resunit_route(const SrnResUnitParams* p, int32_t out[3]);
 
 /* SiFiGAN pitch-dependent dilated-conv operand gather (row a9; un-vendored `sifigan` package, parity unpinned):
  * out (B, T, 3C) = [lrelu(x[t]) | lrelu(x[t - r]) | lrelu(x[t + r])], r = rint(d[b, t] * dilation), zero outside. */
@@ -496,6 +505,11 @@ typedef struct SrnTnGemmParams {
 enum { SRN_TN_ROUTE_GENERAL = 1 };
 int srn_tn_gemm(const SrnTnGemmParams* p, void* stream);
 int64_t srn_tn_gemm_workspace_bytes(const SrnTnGemmParams* p);
+/* The kernel srn_tn_gemm runs for these params, from the very code its launch runs (pure host code, no launch):
+ * out[0] = tile edge (64 or 128), out[1] = K slices (1: stored directly; without a workspace of
+ * srn_tn_gemm_workspace_bytes at a 16-byte aligned address the launch falls back to 1), out[2] = 1 for the scalar-walk
+ * kernel, 0 for the general one.  Returns the launch's validation error where the launch would. */
+int srn_tn_gemm_route(const SrnTnGemmParams* p, int32_t out[3]);
 
 /*
  * Training-mode pieces of the GST style encoder (serenade/modules/gst/style_encoder.py:171-191,235-252 under autograd;

@@ -22,6 +22,8 @@ ROUTE_AUTO, ROUTE_TILED, ROUTE_HALO, ROUTE_GENERIC, ROUTE_STRIP, ROUTE_FAST_FP32
 FAMILY_GENERIC, FAMILY_F32, FAMILY_FAST, FAMILY_HALO, FAMILY_STRIP = 0, 1, 2, 3, 4
 RESUNIT_ROUTE_SHARED = 1  # SrnResUnitParams.route: resunit.hip's exact-fp32 form
 TN_ROUTE_GENERAL = 1  # SrnTnGemmParams.route: the general kernel only
+# implementations srn_hifigan_resunit_route reports
+RESUNIT_FORM_F32, RESUNIT_FORM_SHARED_F32, RESUNIT_FORM_BF16X3 = 0, 1, 2
 
 
 class SrnConvParams(ctypes.Structure):
@@ -117,6 +119,7 @@ _SIGS = {
     "srn_conv_gemm_route": (c_int, [POINTER(SrnConvParams), POINTER(c_int32)]),
     "srn_conv_gemm_forms": (c_int, [POINTER(c_int32), c_int]),
     "srn_hifigan_resunit": (c_int, [POINTER(SrnResUnitParams), _P]),
+    "srn_hifigan_resunit_route": (c_int, [POINTER(SrnResUnitParams), POINTER(c_int32)]),
     "srn_gn_mish_apply": (c_int, [_P, _P, _P, _P, _P, c_int64, _P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
     "srn_resblock_tail": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int,
                                   c_float, c_float, c_int, _P]),
@@ -169,6 +172,7 @@ _SIGS = {
     "srn_token_attn_bwd": (c_int, [_P] * 8 + [c_int] * 4 + [_P]),
     "srn_tn_gemm": (c_int, [POINTER(SrnTnGemmParams), _P]),
     "srn_tn_gemm_workspace_bytes": (c_int64, [POINTER(SrnTnGemmParams)]),
+    "srn_tn_gemm_route": (c_int, [POINTER(SrnTnGemmParams), POINTER(c_int32)]),
     "srn_world_cheaptrick": (c_int, [POINTER(SrnWorldParams), _P]),
     "srn_world_d4c": (c_int, [POINTER(SrnWorldParams), _P]),
     "srn_world_project": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, c_int, _P, c_int, _P]),

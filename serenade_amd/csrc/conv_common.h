@@ -299,6 +299,19 @@ constexpr int SRN_RESUNIT_HALO_MAX = 50;  // the same span as the fused residual
 constexpr int SRN_STRIP_BM = 128;     // conv_strip.hip: output rows per tile (4 waves x 32 rows)
 constexpr int SRN_MAX_KSPLIT = 8;     // conv_splitk.hip: most K slices of one launch
 
+// what resunit.hip's resunit_route decides for one validated srn_hifigan_resunit call
+struct SrnResUnitRoute {
+  int form;         // SRN_RESUNIT_FORM_*
+  int tiles_per_z;  // output tiles per batch item
+  int n_tiles;      // n_batch * tiles_per_z
+  int grid;         // workgroups: min(n_tiles, 512), each walks tiles grid apart
+};
+// intermediate rows per tile, in every form of the kernel
+constexpr int srn_resunit_bmi(const int C) { return C == 32 ? 256 : 128; }
+// resunit_f32.hip: whether that form takes the (validated) call, and its launch
+bool srn_resunit_f32_eligible(const SrnResUnitParams& p, const SrnResUnitRoute& r);
+int srn_resunit_f32_launch(const SrnResUnitParams& p, const SrnResUnitRoute& r, hipStream_t stream);
+
 // lowest tap offset and the span (max - min) of the taps
 inline int srn_tap_span(const SrnConvParams& p, int& lo) {
   lo = p.tap_off[0];

@@ -23,9 +23,6 @@
 
 #include <stdlib.h>
 
-// implemented in resunit_f32.hip: 1 handled, 0 not eligible, < 0 error
-int srn_resunit_f32_try(const SrnResUnitParams& p, hipStream_t stream);
-
 namespace {
 
 template <int C_, int PREC_, int NW_ = 4>
@@ -366,45 +363,76 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
 }
 
 template <class R>
-int launch_resunit(const SrnResUnitParams& p, hipStream_t stream) {
+int launch_resunit(const SrnResUnitParams& p, const SrnResUnitRoute& r, hipStream_t stream) {
   static SrnSmemAttr smem_attr;
   if (const int e = smem_attr.ensure(reinterpret_cast<const void*>(&resunit_kernel<R>), R::SMEM)) return e;
-  const int BMo = R::BMI - (p.k - 1);
-  const int tiles_per_z = (p.T + BMo - 1) / BMo;
-  const int64_t n_tiles = (int64_t)p.n_batch * tiles_per_z;
-  SRN_CHECK_ARG(n_tiles > 0 && n_tiles < (1ll << 31), "resunit: bad tile count %lld", (long long)n_tiles);
-  const int grid = (int)(n_tiles < 512 ? n_tiles : 512);  // persistent: two workgroups per CU
-  hipLaunchKernelGGL((resunit_kernel<R>), dim3(grid), dim3(R::NTH), R::SMEM, stream, p, tiles_per_z, (int)n_tiles);
+  static_assert(R::BMI == srn_resunit_bmi(R::C), "the route's tile height is the kernel's");
+  hipLaunchKernelGGL((resunit_kernel<R>), dim3(r.grid), dim3(R::NTH), R::SMEM, stream, p, r.tiles_per_z, r.n_tiles);
   SRN_CHECK_LAUNCH();
   return 0;
 }
 
-}  // namespace
-
-extern "C" int srn_hifigan_resunit(const SrnResUnitParams* pp, void* stream_) {
+// Validation and the choice of the implementation, stated once: srn_hifigan_resunit launches what this answers and
+// srn_hifigan_resunit_route reports it.
+int resunit_route(const SrnResUnitParams* pp, SrnResUnitRoute& r) {
   SRN_CHECK_ARG(pp != nullptr, "resunit: null params");
   const SrnResUnitParams& p = *pp;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   SRN_CHECK_ARG(p.x && p.w1 && p.b1 && p.w2 && p.b2 && p.out, "resunit: null pointer");
   SRN_CHECK_ARG(p.n_batch > 0 && p.T > 0, "resunit: bad sizes");
   SRN_CHECK_ARG(p.C == 32 || p.C == 64, "resunit: C = %d (this fused kernel takes 32 or 64 channels)", p.C);
   SRN_CHECK_ARG(p.k >= 1 && p.k % 2 == 1 && p.dilation >= 1 && (p.k - 1) * p.dilation <= SRN_RESUNIT_HALO_MAX,
                 "resunit: kernel %d / dilation %d outside the staged halo (%d rows)", p.k, p.dilation, SRN_RESUNIT_HALO_MAX);
-  SRN_CHECK_ARG(p.out != p.x && p.out != p.res2 - 0 ? true : p.out != p.x, "resunit: out must not alias x");
+  SRN_CHECK_ARG(p.out != p.x, "resunit: out must not alias x");
+  // x and the weights are read in 16-byte pieces; res2 and out one float at a time in every form (plain loads and
+  // stores here, 4-byte buffer accesses in resunit_f32.hip): they and their batch strides need no more than a float's
+  // alignment
   SRN_CHECK_ARG(((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.w1) |
                   reinterpret_cast<uintptr_t>(p.w2)) & 15) == 0 && p.x_bs % 4 == 0,
                 "resunit: x / w1 / w2 must be 16-byte aligned");
+  const int BMo = srn_resunit_bmi(p.C) - (p.k - 1);
+  r.tiles_per_z = (p.T + BMo - 1) / BMo;
+  const int64_t n_tiles = (int64_t)p.n_batch * r.tiles_per_z;
+  SRN_CHECK_ARG(n_tiles > 0 && n_tiles < (1ll << 31), "resunit: bad tile count %lld", (long long)n_tiles);
+  r.n_tiles = (int)n_tiles;
+  r.grid = (int)(n_tiles < 512 ? n_tiles : 512);  // persistent: two workgroups per CU
   if (p.precision == SRN_PREC_BF16X3) {
     SRN_CHECK_ARG(p.w1_hi && p.w2_hi, "resunit: split-bf16 mode needs the weight planes w1_hi / w2_hi");
-    return p.C == 32 ? launch_resunit<RCfg<32, 1>>(p, stream) : launch_resunit<RCfg<64, 1>>(p, stream);
+    r.form = SRN_RESUNIT_FORM_BF16X3;
+  } else {
+    // exact fp32: resunit_f32.hip's form of this kernel (same results bit for bit, ~no vector-ALU work beside the fp32
+    // MFMAs) where it is eligible; route SRN_RESUNIT_ROUTE_SHARED keeps this file's instantiation (A-B timing,
+    // bit-identity test)
+    r.form = p.route != SRN_RESUNIT_ROUTE_SHARED && srn_resunit_f32_eligible(p, r) ? SRN_RESUNIT_FORM_F32
+                                                                                   : SRN_RESUNIT_FORM_SHARED_F32;
   }
-  // exact fp32: resunit_f32.hip's form of this kernel (same results bit for bit, ~no vector-ALU work beside the fp32
-  // MFMAs); route SRN_RESUNIT_ROUTE_SHARED keeps this file's instantiation (A-B timing, bit-identity test)
-  if (p.route != SRN_RESUNIT_ROUTE_SHARED) {
-    const int r = srn_resunit_f32_try(p, stream);
-    if (r != 0) return r < 0 ? r : 0;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int srn_hifigan_resunit_route(const SrnResUnitParams* pp, int32_t out[3]) {
+  SRN_CHECK_ARG(out != nullptr, "resunit_route: null out");
+  SrnResUnitRoute r;
+  if (const int e = resunit_route(pp, r)) return e;
+  out[0] = r.form;
+  out[1] = r.tiles_per_z;
+  out[2] = r.grid;
+  return 0;
+}
+
+extern "C" int srn_hifigan_resunit(const SrnResUnitParams* pp, void* stream_) {
+  SrnResUnitRoute r;
+  if (const int e = resunit_route(pp, r)) return e;
+  const SrnResUnitParams& p = *pp;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  switch (r.form) {
+    case SRN_RESUNIT_FORM_BF16X3:
+      return p.C == 32 ? launch_resunit<RCfg<32, 1>>(p, r, stream) : launch_resunit<RCfg<64, 1>>(p, r, stream);
+    case SRN_RESUNIT_FORM_F32:
+      return srn_resunit_f32_launch(p, r, stream);
+    default:
+      // eight waves per workgroup (A/B on the B = 8 x T = 1024 vocoder, 4 -> 8 waves: k 3 units 0.62 -> 0.51 ms,
+      // k 7 1.17 -> 1.05, k 11 1.74 -> 1.61 at C = 64; all 18 units 16.7 -> 14.9 ms)
+      return p.C == 32 ? launch_resunit<RCfg<32, 0, 8>>(p, r, stream) : launch_resunit<RCfg<64, 0, 8>>(p, r, stream);
   }
-  // eight waves per workgroup (A/B on the B = 8 x T = 1024 vocoder, 4 -> 8 waves: k 3 units 0.62 -> 0.51 ms,
-  // k 7 1.17 -> 1.05, k 11 1.74 -> 1.61 at C = 64; all 18 units 16.7 -> 14.9 ms)
-  return p.C == 32 ? launch_resunit<RCfg<32, 0, 8>>(p, stream) : launch_resunit<RCfg<64, 0, 8>>(p, stream);
 }

@@ -255,26 +255,26 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
 }
 
 template <class R>
-int launch_unit(const SrnResUnitParams& p, hipStream_t stream) {
+int launch_unit(const SrnResUnitParams& p, const SrnResUnitRoute& r, hipStream_t stream) {
   static SrnSmemAttr smem_attr;
   if (const int e = smem_attr.ensure(reinterpret_cast<const void*>(&resunit_f32_kernel<R>), R::SMEM)) return e;
-  const int BMo = R::BMI - (p.k - 1);
-  const int tiles_per_z = (p.T + BMo - 1) / BMo;
-  const int64_t n_tiles = (int64_t)p.n_batch * tiles_per_z;
-  if (n_tiles <= 0 || n_tiles >= (1ll << 26)) return 0;
-  const int grid = (int)(n_tiles < 512 ? n_tiles : 512);  // persistent: two workgroups per CU
-  hipLaunchKernelGGL((resunit_f32_kernel<R>), dim3(grid), dim3(NTH), R::SMEM, stream, p, tiles_per_z, (int)n_tiles,
-                     make_fdiv((uint32_t)tiles_per_z));
+  static_assert(R::BMI == srn_resunit_bmi(R::C), "the route's tile height is the kernel's");
+  hipLaunchKernelGGL((resunit_f32_kernel<R>), dim3(r.grid), dim3(NTH), R::SMEM, stream, p, r.tiles_per_z, r.n_tiles,
+                     make_fdiv((uint32_t)r.tiles_per_z));
   SRN_CHECK_LAUNCH();
-  return 1;
+  return 0;
 }
 
 }  // namespace
 
-// Returns 1 if the launch was handled, 0 if the unit is not eligible (the caller runs resunit.hip's fp32 form), < 0 on
-// error.  `p` has been validated by srn_hifigan_resunit.
-int srn_resunit_f32_try(const SrnResUnitParams& p, hipStream_t stream) {
-  if (!(p.slope >= 0.f && p.slope <= 1.f)) return 0;
-  if ((int64_t)p.T * p.C * 4 >= 0x7fffffffll) return 0;  // 32-bit byte offsets inside one item
-  return p.C == 32 ? launch_unit<UCfg<32>>(p, stream) : launch_unit<UCfg<64>>(p, stream);
+// Whether this form takes the call; otherwise the caller runs resunit.hip's fp32 form.  `p` has been validated and `r`
+// holds its tile counts (resunit.hip's resunit_route).
+bool srn_resunit_f32_eligible(const SrnResUnitParams& p, const SrnResUnitRoute& r) {
+  if (!(p.slope >= 0.f && p.slope <= 1.f)) return false;           // LeakyReLU as max(x, slope x)
+  if ((int64_t)p.T * p.C * 4 >= 0x7fffffffll) return false;        // 32-bit byte offsets inside one item
+  return r.n_tiles < (1 << 26);                                    // fdiv's range
+}
+
+int srn_resunit_f32_launch(const SrnResUnitParams& p, const SrnResUnitRoute& r, hipStream_t stream) {
+  return p.C == 32 ? launch_unit<UCfg<32>>(p, r, stream) : launch_unit<UCfg<64>>(p, r, stream);
 }

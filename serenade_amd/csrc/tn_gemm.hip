@@ -413,21 +413,17 @@ int tile_edge(const SrnTnGemmParams& p) {
   return 128;
 }
 
-}  // namespace
+// Validation, tile edge, K slices and the choice between the two kernels, stated once: srn_tn_gemm launches what this
+// answers and srn_tn_gemm_route reports it.
+struct TnRoute {
+  int TB, ks, k_per;  // tile edge (64 / 128), K slices (1: no workspace pass), contraction rows per slice
+  int m_tiles, n_tiles;
+  bool lean;          // tn_lean_kernel, else tn_gemm_kernel
+};
 
-extern "C" int64_t srn_tn_gemm_workspace_bytes(const SrnTnGemmParams* p) {
-  if (p == nullptr || p->M <= 0 || p->N <= 0 || p->n_items <= 0 || p->T_a <= 0 || p->n_shifts <= 0) return 0;
-  int k_per = 0;
-  const int TB = tile_edge(*p);
-  const int ks = plan_split(*p, TB, k_per);
-  if (ks <= 1) return 0;
-  return ws_floats(*p, ks) * (int64_t)sizeof(float);
-}
-
-extern "C" int srn_tn_gemm(const SrnTnGemmParams* pp, void* stream_) {
+int tn_route(const SrnTnGemmParams* pp, TnRoute& r) {
   SRN_CHECK_ARG(pp != nullptr, "tn_gemm: null params");
   const SrnTnGemmParams& p = *pp;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   SRN_CHECK_ARG(p.a && p.b && p.out, "tn_gemm: null a / b / out");
   SRN_CHECK_ARG(p.n_batch > 0 && p.n_head > 0 && p.n_items > 0 && p.T_a > 0 && p.T_b > 0 && p.M > 0 && p.N > 0,
                 "tn_gemm: bad sizes");
@@ -448,31 +444,59 @@ extern "C" int srn_tn_gemm(const SrnTnGemmParams* pp, void* stream_) {
                                         (reinterpret_cast<uintptr_t>(p.colsum) & 15) == 0),
                 "tn_gemm: colsum needs one problem (n_batch = n_head = 1), M %% 4 == 0 and a 16-byte aligned pointer");
   SRN_CHECK_ARG(p.len_b == nullptr || p.n_inner <= 1, "tn_gemm: len_b is per item of a one-level item grid");
-  int k_per = 0;
-  const int TB = tile_edge(p);
-  int ks = plan_split(p, TB, k_per);
-  if (ks > 1) {
-    const int64_t need = ws_floats(p, ks) * (int64_t)sizeof(float);
+  r.TB = tile_edge(p);
+  r.ks = plan_split(p, r.TB, r.k_per);
+  if (r.ks > 1) {
+    const int64_t need = ws_floats(p, r.ks) * (int64_t)sizeof(float);
     if (p.ws == nullptr || p.ws_bytes < need || (reinterpret_cast<uintptr_t>(p.ws) & 15) != 0) {
-      ks = 1;  // no (or too small a) workspace: correct, just fewer workgroups
-      k_per = (int)(((int64_t)p.n_items * p.T_a + BK - 1) / BK * BK);
+      r.ks = 1;  // no (or too small a) workspace: correct, just fewer workgroups
+      r.k_per = (int)(((int64_t)p.n_items * p.T_a + BK - 1) / BK * BK);
     }
   }
-  const int m_tiles = (p.M + TB - 1) / TB, n_tiles = (p.N + TB - 1) / TB;
-  const int64_t gz = (int64_t)p.n_batch * p.n_head * ks;
-  SRN_CHECK_ARG(gz <= 65535 && (int64_t)m_tiles * n_tiles < (1ll << 31), "tn_gemm: grid too large");
-  const dim3 grid(m_tiles * n_tiles, p.n_shifts, (unsigned)gz);
+  r.m_tiles = (p.M + r.TB - 1) / r.TB, r.n_tiles = (p.N + r.TB - 1) / r.TB;
+  const int64_t gz = (int64_t)p.n_batch * p.n_head * r.ks;
+  SRN_CHECK_ARG(gz <= 65535 && (int64_t)r.m_tiles * r.n_tiles < (1ll << 31), "tn_gemm: grid too large");
   // the scalar-walk form: every slab inside one item, 32-bit byte offsets inside an item (route SRN_TN_ROUTE_GENERAL:
   // A-B timing and the bit-identity test keep the general kernel)
-  const bool lean = p.route != SRN_TN_ROUTE_GENERAL && p.n_inner <= 1 && p.T_a % BK == 0 && k_per % BK == 0 &&
+  r.lean = p.route != SRN_TN_ROUTE_GENERAL && p.n_inner <= 1 && p.T_a % BK == 0 && r.k_per % BK == 0 &&
                     (int64_t)p.T_a * p.lda * 4 < 0x7fffffffll &&
                     ((int64_t)p.T_b + (int64_t)p.T_a * p.stride + 64) * p.ldb * 4 < 0x7fffffffll;
-  auto kern = lean ? (TB == 64 ? tn_lean_kernel<64> : tn_lean_kernel<128>)
-                   : (TB == 64 ? tn_gemm_kernel<64> : tn_gemm_kernel<128>);
-  hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, p, m_tiles, n_tiles, ks, k_per);
-  if (ks > 1) {
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t srn_tn_gemm_workspace_bytes(const SrnTnGemmParams* p) {
+  if (p == nullptr || p->M <= 0 || p->N <= 0 || p->n_items <= 0 || p->T_a <= 0 || p->n_shifts <= 0) return 0;
+  int k_per = 0;
+  const int TB = tile_edge(*p);
+  const int ks = plan_split(*p, TB, k_per);
+  if (ks <= 1) return 0;
+  return ws_floats(*p, ks) * (int64_t)sizeof(float);
+}
+
+extern "C" int srn_tn_gemm_route(const SrnTnGemmParams* pp, int32_t out[3]) {
+  SRN_CHECK_ARG(out != nullptr, "tn_gemm_route: null out");
+  TnRoute r;
+  if (const int e = tn_route(pp, r)) return e;
+  out[0] = r.TB;
+  out[1] = r.ks;
+  out[2] = r.lean ? 1 : 0;
+  return 0;
+}
+
+extern "C" int srn_tn_gemm(const SrnTnGemmParams* pp, void* stream_) {
+  TnRoute r;
+  if (const int e = tn_route(pp, r)) return e;
+  const SrnTnGemmParams& p = *pp;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const dim3 grid(r.m_tiles * r.n_tiles, p.n_shifts, (unsigned)((int64_t)p.n_batch * p.n_head * r.ks));
+  auto kern = r.lean ? (r.TB == 64 ? tn_lean_kernel<64> : tn_lean_kernel<128>)
+                     : (r.TB == 64 ? tn_gemm_kernel<64> : tn_gemm_kernel<128>);
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, p, r.m_tiles, r.n_tiles, r.ks, r.k_per);
+  if (r.ks > 1) {
     const int64_t n4 = (int64_t)p.n_batch * p.n_head * p.M * p.n_shifts * p.N / 4 + (p.colsum != nullptr ? p.M / 4 : 0);
-    hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, p, ks);
+    hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, p, r.ks);
   }
   SRN_CHECK_LAUNCH();
   return 0;

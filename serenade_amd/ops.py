@@ -156,14 +156,15 @@ class ResUnitOp(_StructOp):
         super().__init__("srn_hifigan_resunit", kw)
 
     def _fill(self, *, x, w1, b1, w2, b2, out, n_batch, T, C, k, dilation, slope, res2=None, post_div=0.0,
-               precision=None, route=0):
+               precision=None, route=0, x_bs=None, res2_bs=None, out_bs=None):
         p = SrnResUnitParams()
         p.n_batch, p.T, p.C, p.k, p.dilation, p.slope = int(n_batch), int(T), int(C), int(k), int(dilation), float(slope)
-        p.x, p.x_bs = _ptr(x), int(T) * int(C)
+        item = int(T) * int(C)  # batch strides: contiguous items unless given
+        p.x, p.x_bs = _ptr(x), item if x_bs is None else int(x_bs)
         p.w1, p.b1, p.w2, p.b2 = _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2)
-        p.res2, p.res2_bs = _ptr(res2), int(T) * int(C)
+        p.res2, p.res2_bs = _ptr(res2), item if res2_bs is None else int(res2_bs)
         p.post_div = float(post_div)
-        p.out, p.out_bs = _ptr(out), int(T) * int(C)
+        p.out, p.out_bs = _ptr(out), item if out_bs is None else int(out_bs)
         p.precision = int(DEFAULT_PRECISION if precision is None else precision)
         p.route = int(route)  # _lib.RESUNIT_ROUTE_SHARED: resunit.hip's exact-fp32 form (testing / A-B timing)
         self._wplanes = None

@@ -520,20 +520,26 @@ def emul_call(name, a):
 
 
 def emul_resunit(kw):
-    """srn_hifigan_resunit: y = conv2(lrelu(conv1(lrelu(x)))) + x [+ res2] [/ post_div], channels-last views"""
+    """srn_hifigan_resunit: y = conv2(lrelu(conv1(lrelu(x)))) + x [+ res2] [/ post_div], channels-last views; items
+    x_bs / res2_bs / out_bs apart (T * C unless given)"""
     g = kw.get
     B, T, C, k, d, slope = g("n_batch"), g("T"), g("C"), g("k"), g("dilation"), g("slope")
-    x = _v(g("x"), B * T * C).reshape(B, T, C)
+
+    def items(t, bs):  # (B, T, C) view of a tensor or (tensor, offset) with its batch stride
+        f, o = _flat(t)
+        return torch.as_strided(f, (B, T, C), (bs or T * C, C, 1), o + f.storage_offset())
+
+    x = items(g("x"), g("x_bs"))
     w1 = g("w1").reshape(C, k, C).permute(0, 2, 1)  # packed [C_out][k][C_in] -> torch (C_out, C_in, k)
     w2 = g("w2").reshape(C, k, C).permute(0, 2, 1)
     xt = F.conv1d(F.leaky_relu(x.transpose(1, 2), slope), w1, g("b1"), padding=(k - 1) // 2 * d, dilation=d)
     xt = F.conv1d(F.leaky_relu(xt, slope), w2, g("b2"), padding=(k - 1) // 2)
     y = xt.transpose(1, 2) + x
     if g("res2") is not None:
-        y = y + _v(g("res2"), B * T * C).reshape(B, T, C)
+        y = y + items(g("res2"), g("res2_bs"))
     if g("post_div", 0.0) not in (0.0, 1.0):
         y = y / g("post_div")
-    _v(g("out"), B * T * C).reshape(B, T, C)[:] = y
+    items(g("out"), g("out_bs"))[:] = y
 
 
 def emul_tn_gemm(kw):
@@ -569,7 +575,8 @@ def emul_tn_gemm(kw):
                         end = min(T_b, int(len_b.view(-1)[zb * g("n_items") + it]))
                     ok = (tb >= 0) & (tb < end)
                     rows = torch.as_strided(b, (T_b, N), (g("ldb"), 1), b0).double()[tb.clamp(0, T_b - 1)]
-                    acc += am.t() @ (rows * ok[:, None])
+                    # (a select, not a product: whatever the rows outside [0, end) hold, they count as zero)
+                    acc += am.t() @ torch.where(ok[:, None], rows, torch.zeros((), dtype=torch.float64))
                 o0 = oo + zb * g("out_bs") + zh * g("out_hs") + j * N
                 torch.as_strided(out, (M, N), (g("ldc"), 1), o0).copy_((acc * g("alpha")).float())
 

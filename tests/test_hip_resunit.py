@@ -5,6 +5,9 @@
   sequence ends inside / across tiles, with and without the stage sum / mean epilogue;
 * split-K (conv_splitk.hip): small tile grids with deep contractions take the sliced path (asserted through
   srn_conv_gemm_workspace_bytes) and agree with the executable spec, with every epilogue feature it reduces.
+
+The per-element float64 sweep of every form of the residual unit at its edge shapes (tile seams, the persistent tile
+loop, batch strides, in-place res2, slopes outside [0, 1]) is tests/test_hip_mfmasweep.py (cases: tests/_mfma_cases.py).
 """
 import ctypes
 

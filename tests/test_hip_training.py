@@ -439,7 +439,9 @@ def test_memset_guard_sees_torch_reductions_and_clears_the_product_step(dev):
         training.GraphedStep(model, training.AdamW(model), 2, 256, warmup=0)
 
 
-# ---- srn_tn_gemm: contractions over time (weight gradients, dK, dV) against fp64 torch
+# ---- srn_tn_gemm: contractions over time (weight gradients, dK, dV) against fp64 torch, at the training step's shapes.
+#      The per-element sweep of every kernel form at its edge shapes (both tile edges, sliced or not, two-level items, len_b
+#      over a batch, 16 shifts, the workspace fall-backs) is tests/test_hip_mfmasweep.py (cases: tests/_mfma_cases.py)
 @pytest.mark.parametrize("case", ["wgrad_k3", "wgrad_stride2", "wgrad_valid", "wgrad_tiny_k", "attn", "ragged_m"])
 def test_tn_gemm_against_fp64(dev, case):
     from serenade_amd.ops import TnGemmOp
