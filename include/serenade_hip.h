@@ -323,6 +323,25 @@ int srn_logmel(const float* spec, const float* mel_t, float* out, int64_t frames
  * gmax_ws: B uint32 of scratch. */
 int srn_loudness(const float* spec, const float* a_weight_db, uint32_t* gmax_ws, float* out, int B, int frames,
                  int n_bins, int ld, float amin, float top_db, float add_eps, void* stream);
+/* The same three for a padded batch of unequal utterances, each item treated as its own B = 1 call treats it (the
+ * reference runs both functions on one utterance at a time, preprocess.py:435-447,471-472). */
+/* numpy.pad(x[b][:L], pad, "constant") with L = min(lens[b], n) (librosa.stft's default pad_mode since 0.10, which
+ * loudness_extract's call preprocess.py:131 takes): out (B, ld)[b][pad + j] = x[b][j] for j < L, 0 everywhere else up
+ * to ld; x (B, n) at row stride x_bs is not read at j >= L.  lens: B device int32.  The constant-mode twin of
+ * srn_pad_ragged. */
+int srn_pad_ragged_zero(const float* x, int64_t x_bs, const int32_t* lens, float* out, int B, int n, int pad, int ld,
+                        void* stream);
+/* srn_logmel on spec (B, T, ld) -> out (B, T, n_mels) with per-item frame counts `frames` (B device int32): rows
+ * t < min(frames[b], T) are srn_logmel's (preprocess.py:176-203), rows at or past it are 0 and nothing of spec is read
+ * for them. */
+int srn_logmel_ragged(const float* spec, const float* mel_t, const int32_t* frames, float* out, int B, int T,
+                      int n_bins, int ld, int n_mels, float eps, int log_mode, void* stream);
+/* srn_loudness on spec (B, T, ld) -> out (B, T) with per-item frame counts: the top_db floor of item b comes from the
+ * maximum power over its own frames t < min(frames[b], T) only (power_to_db of one utterance, preprocess.py:126-137);
+ * rows at or past it are 0 and not read.  gmax_ws: B uint32 of scratch. */
+int srn_loudness_ragged(const float* spec, const float* a_weight_db, const int32_t* frames, uint32_t* gmax_ws,
+                        float* out, int B, int T, int n_bins, int ld, float amin, float top_db, float add_eps,
+                        void* stream);
 
 /*
  * Training step of the estimator: the backward of the decoder blocks that CFM.compute_loss

@@ -140,6 +140,9 @@ _SIGS = {
     "srn_pad_signal": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "srn_logmel": (c_int, [_P, _P, _P, c_int64, c_int, c_int, c_int, c_float, c_int, _P]),
     "srn_loudness": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, _P]),
+    "srn_pad_ragged_zero": (c_int, [_P, c_int64, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "srn_logmel_ragged": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
+    "srn_loudness_ragged": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, _P]),
     "srn_gru_recur_last": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "srn_style_token_attention_kv": (c_int, [_P] * 8 + [c_int] * 5 + [_P]),
     "srn_rowln_fwd": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int, c_float, _P]),

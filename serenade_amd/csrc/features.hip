@@ -5,7 +5,8 @@
 // = n_fft / 16 taps, hop / 16 rows of stride, weights = window x DFT basis, [re | im] output columns); this file holds
 // the byte-moving and elementwise ends: reflection padding, magnitude -> mel -> log, and power -> dB (with the
 // per-utterance top_db floor) -> A-weighting -> amplitude -> frame mean -> log.  All HBM-bound and tiny next to the
-// model (8.4 MFLOP per frame for the loudness STFT, 0.5 for the mel one).
+// model (8.4 MFLOP per frame for the loudness STFT, 0.5 for the mel one).  Each of the three ends has a ragged twin for
+// a padded batch of unequal utterances (per-item sample / frame counts): every item gets what its own B = 1 call gets.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -31,14 +32,12 @@ __global__ __launch_bounds__(256) void pad_signal_kernel(const float* __restrict
   }
 }
 
-// one workgroup per frame: |X| of the nb bins into LDS, then mel bin m = threadIdx (mel_t is (nb, n_mels): lanes read
-// consecutive addresses), out = log(max(eps, dot))
-__global__ __launch_bounds__(128) void logmel_kernel(const float* __restrict__ spec, const float* __restrict__ mel_t,
-                                                     float* __restrict__ out, const int nb, const int ld,
-                                                     const int n_mels, const float eps, const int log_mode) {
-  extern __shared__ float mag[];
-  const int64_t fr = blockIdx.x;
-  const float* row = spec + fr * ld;
+// one frame by one workgroup of 128: |X| of the nb bins into LDS (mag), then mel bin m = threadIdx (mel_t is
+// (nb, n_mels): lanes read consecutive addresses), o[m] = log(max(eps, dot)).  The arithmetic of logmel_kernel and
+// logmel_ragged_kernel, stated once.
+__device__ __forceinline__ void logmel_row(const float* __restrict__ row, const float* __restrict__ mel_t,
+                                           float* __restrict__ o, float* mag, const int nb, const int n_mels,
+                                           const float eps, const int log_mode) {
   for (int f = threadIdx.x; f < nb; f += 128) {
     const float re = row[f], im = row[nb + f];
     mag[f] = sqrtf(re * re + im * im);
@@ -48,7 +47,50 @@ __global__ __launch_bounds__(128) void logmel_kernel(const float* __restrict__ s
     float a = 0.f;
     for (int f = 0; f < nb; ++f) a = fmaf(mag[f], mel_t[f * n_mels + m], a);
     a = fmaxf(a, eps);
-    out[fr * n_mels + m] = log_mode == 10 ? log10f(a) : (log_mode == 2 ? log2f(a) : logf(a));
+    o[m] = log_mode == 10 ? log10f(a) : (log_mode == 2 ? log2f(a) : logf(a));
+  }
+}
+
+// one workgroup per frame
+__global__ __launch_bounds__(128) void logmel_kernel(const float* __restrict__ spec, const float* __restrict__ mel_t,
+                                                     float* __restrict__ out, const int nb, const int ld,
+                                                     const int n_mels, const float eps, const int log_mode) {
+  extern __shared__ float mag[];
+  const int64_t fr = blockIdx.x;
+  logmel_row(spec + fr * ld, mel_t, out + fr * n_mels, mag, nb, n_mels, eps, log_mode);
+}
+
+// one workgroup per (frame, item): logmel_row on the frames t < frames[b]; a frame at or past it is written as 0 and
+// its workgroup leaves before it loads anything of spec
+__global__ __launch_bounds__(128) void logmel_ragged_kernel(const float* __restrict__ spec,
+                                                            const float* __restrict__ mel_t,
+                                                            const int32_t* __restrict__ frames,
+                                                            float* __restrict__ out, const int T, const int nb,
+                                                            const int ld, const int n_mels, const float eps,
+                                                            const int log_mode) {
+  extern __shared__ float mag[];
+  const int t = blockIdx.x, b = blockIdx.y;
+  const int64_t fr = (int64_t)b * T + t;
+  float* o = out + fr * n_mels;
+  if (t >= min(frames[b], T)) {  // the same in every lane: the whole workgroup leaves
+    for (int m = threadIdx.x; m < n_mels; m += 128) o[m] = 0.f;
+    return;
+  }
+  logmel_row(spec + fr * ld, mel_t, o, mag, nb, n_mels, eps, log_mode);
+}
+
+// out[b][pad + j] = x[b][j] for j < L = min(lens[b], n), 0 everywhere else up to ld (numpy.pad mode="constant" of the
+// item on its own); x[b][j] is not read for j >= L
+__global__ __launch_bounds__(256) void pad_ragged_zero_kernel(const float* __restrict__ x, const int64_t x_bs,
+                                                              const int32_t* __restrict__ lens,
+                                                              float* __restrict__ out, const int n, const int pad,
+                                                              const int ld) {
+  const int b = blockIdx.y;
+  const int L = min(lens[b], n);
+  const float* xb = x + (int64_t)b * x_bs;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < ld; i += gridDim.x * 256) {
+    const int j = i - pad;
+    out[(int64_t)b * ld + i] = (j >= 0 && j < L) ? xb[j] : 0.f;
   }
 }
 
@@ -58,32 +100,48 @@ __global__ void zero_u32_kernel(unsigned* __restrict__ p, const int n) {
   if (i < n) p[i] = 0u;
 }
 
+// the running maximum of one frame's bin powers, a workgroup of 256 striding over the bins
+__device__ __forceinline__ float power_row_max(const float* __restrict__ row, const int nb, float m) {
+  for (int f = threadIdx.x; f < nb; f += 256) {
+    const float re = row[f], im = row[nb + f];
+    m = fmaxf(m, re * re + im * im);
+  }
+  return m;
+}
+
 // per-utterance maximum of the power spectrogram (non-negative floats order like their bit patterns, so an integer
 // atomicMax gives a bit-reproducible result); gmax must be zeroed by the caller
 __global__ __launch_bounds__(256) void power_max_kernel(const float* __restrict__ spec, unsigned* __restrict__ gmax,
                                                         const int frames, const int nb, const int ld) {
   const int b = blockIdx.y;
   float m = 0.f;
-  for (int fr = blockIdx.x; fr < frames; fr += gridDim.x) {
-    const float* row = spec + ((int64_t)b * frames + fr) * ld;
-    for (int f = threadIdx.x; f < nb; f += 256) {
-      const float re = row[f], im = row[nb + f];
-      m = fmaxf(m, re * re + im * im);
-    }
-  }
+  for (int fr = blockIdx.x; fr < frames; fr += gridDim.x)
+    m = power_row_max(spec + ((int64_t)b * frames + fr) * ld, nb, m);
   m = wave_max(m);
   if ((threadIdx.x & 63) == 0) atomicMax(gmax + b, __float_as_uint(m));
 }
 
-// one workgroup per frame: mean over bins of 10^((max(10 log10(max(amin, p)), top) + A[f]) / 20), then log(. + 1e-5)
-__global__ __launch_bounds__(256) void loudness_kernel(const float* __restrict__ spec, const float* __restrict__ aw,
-                                                       const unsigned* __restrict__ gmax, float* __restrict__ out,
-                                                       const int frames, const int nb, const int ld, const float amin,
-                                                       const float top_db, const float add_eps) {
-  __shared__ float red[4];
-  const int b = blockIdx.y, fr = blockIdx.x;
-  const float floor_db = 10.f * log10f(fmaxf(amin, __uint_as_float(gmax[b]))) - top_db;
-  const float* row = spec + ((int64_t)b * frames + fr) * ld;
+// the same over the item's own frames t < frames[b] of a (B, T) batch: rows at or past it are not read
+__global__ __launch_bounds__(256) void power_max_ragged_kernel(const float* __restrict__ spec,
+                                                               const int32_t* __restrict__ frames,
+                                                               unsigned* __restrict__ gmax, const int T, const int nb,
+                                                               const int ld) {
+  const int b = blockIdx.y;
+  const int len = min(frames[b], T);
+  if ((int)blockIdx.x >= len) return;
+  float m = 0.f;
+  for (int fr = blockIdx.x; fr < len; fr += gridDim.x) m = power_row_max(spec + ((int64_t)b * T + fr) * ld, nb, m);
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) atomicMax(gmax + b, __float_as_uint(m));
+}
+
+// one frame by one workgroup of 256: mean over bins of 10^((max(10 log10(max(amin, p)), top) + A[f]) / 20), then
+// log(. + add_eps); `top` from the utterance's maximum power gmax_b.  The arithmetic of loudness_kernel and
+// loudness_ragged_kernel, stated once; red: 4 floats of LDS.
+__device__ __forceinline__ float loudness_row(const float* __restrict__ row, const float* __restrict__ aw,
+                                              const unsigned gmax_b, float* red, const int nb, const float amin,
+                                              const float top_db, const float add_eps) {
+  const float floor_db = 10.f * log10f(fmaxf(amin, __uint_as_float(gmax_b))) - top_db;
   float s = 0.f;
   for (int f = threadIdx.x; f < nb; f += 256) {
     const float re = row[f], im = row[nb + f];
@@ -93,7 +151,37 @@ __global__ __launch_bounds__(256) void loudness_kernel(const float* __restrict__
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) out[(int64_t)b * frames + fr] = logf(((red[0] + red[1]) + (red[2] + red[3])) / nb + add_eps);
+  return logf(((red[0] + red[1]) + (red[2] + red[3])) / nb + add_eps);
+}
+
+// one workgroup per frame
+__global__ __launch_bounds__(256) void loudness_kernel(const float* __restrict__ spec, const float* __restrict__ aw,
+                                                       const unsigned* __restrict__ gmax, float* __restrict__ out,
+                                                       const int frames, const int nb, const int ld, const float amin,
+                                                       const float top_db, const float add_eps) {
+  __shared__ float red[4];
+  const int b = blockIdx.y, fr = blockIdx.x;
+  const float v = loudness_row(spec + ((int64_t)b * frames + fr) * ld, aw, gmax[b], red, nb, amin, top_db, add_eps);
+  if (threadIdx.x == 0) out[(int64_t)b * frames + fr] = v;
+}
+
+// one workgroup per (frame, item): loudness_row on the frames t < frames[b] with the item's own maximum; a frame at or
+// past it is written as 0 and its workgroup leaves before it loads anything of spec, aw or gmax
+__global__ __launch_bounds__(256) void loudness_ragged_kernel(const float* __restrict__ spec,
+                                                              const float* __restrict__ aw,
+                                                              const int32_t* __restrict__ frames,
+                                                              const unsigned* __restrict__ gmax,
+                                                              float* __restrict__ out, const int T, const int nb,
+                                                              const int ld, const float amin, const float top_db,
+                                                              const float add_eps) {
+  __shared__ float red[4];
+  const int b = blockIdx.y, t = blockIdx.x;
+  if (t >= min(frames[b], T)) {  // the same in every lane: the whole workgroup leaves
+    if (threadIdx.x == 0) out[(int64_t)b * T + t] = 0.f;
+    return;
+  }
+  const float v = loudness_row(spec + ((int64_t)b * T + t) * ld, aw, gmax[b], red, nb, amin, top_db, add_eps);
+  if (threadIdx.x == 0) out[(int64_t)b * T + t] = v;
 }
 
 }  // namespace
@@ -133,6 +221,48 @@ extern "C" int srn_loudness(const float* spec, const float* a_weight_db, unsigne
   hipLaunchKernelGGL(power_max_kernel, dim3(frames < 512 ? frames : 512, B), dim3(256), 0, st, spec, gmax_ws, frames,
                      n_bins, ld);
   hipLaunchKernelGGL(loudness_kernel, dim3(frames, B), dim3(256), 0, st, spec, a_weight_db, gmax_ws, out, frames,
+                     n_bins, ld, amin, top_db, add_eps);
+  SRN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int srn_pad_ragged_zero(const float* x, int64_t x_bs, const int32_t* lens, float* out, int B, int n, int pad,
+                                   int ld, void* stream) {
+  SRN_CHECK_ARG(x && lens && out, "pad_ragged_zero: null pointer");
+  SRN_CHECK_ARG(B > 0 && B <= 65535 && n > 0 && pad >= 0 && ld >= n + 2 * pad && x_bs >= n,
+                "pad_ragged_zero: bad sizes (B %d, n %d, pad %d, ld %d, x_bs %lld)", B, n, pad, ld, (long long)x_bs);
+  int bx = (ld + 255) / 256;
+  bx = bx > 4096 ? 4096 : bx;
+  hipLaunchKernelGGL(pad_ragged_zero_kernel, dim3(bx, B), dim3(256), 0, (hipStream_t)stream, x, x_bs, lens, out, n,
+                     pad, ld);
+  SRN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int srn_logmel_ragged(const float* spec, const float* mel_t, const int32_t* frames, float* out, int B,
+                                 int T, int n_bins, int ld, int n_mels, float eps, int log_mode, void* stream) {
+  SRN_CHECK_ARG(spec && mel_t && frames && out, "logmel_ragged: null pointer");
+  SRN_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && n_bins > 0 && n_bins <= 8192 && ld >= 2 * n_bins && n_mels > 0 &&
+                    (log_mode == 0 || log_mode == 2 || log_mode == 10),
+                "logmel_ragged: bad args (B %d, T %d, n_bins %d, ld %d, n_mels %d, log_mode %d)", B, T, n_bins, ld,
+                n_mels, log_mode);
+  hipLaunchKernelGGL(logmel_ragged_kernel, dim3(T, B), dim3(128), (size_t)n_bins * sizeof(float), (hipStream_t)stream,
+                     spec, mel_t, frames, out, T, n_bins, ld, n_mels, eps, log_mode);
+  SRN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int srn_loudness_ragged(const float* spec, const float* a_weight_db, const int32_t* frames,
+                                   unsigned* gmax_ws, float* out, int B, int T, int n_bins, int ld, float amin,
+                                   float top_db, float add_eps, void* stream) {
+  SRN_CHECK_ARG(spec && a_weight_db && frames && gmax_ws && out, "loudness_ragged: null pointer");
+  SRN_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && n_bins > 0 && ld >= 2 * n_bins,
+                "loudness_ragged: bad args (B %d, T %d, n_bins %d, ld %d)", B, T, n_bins, ld);
+  hipStream_t st = (hipStream_t)stream;
+  srn_zero_u32(gmax_ws, B, st);
+  hipLaunchKernelGGL(power_max_ragged_kernel, dim3(T < 512 ? T : 512, B), dim3(256), 0, st, spec, frames, gmax_ws, T,
+                     n_bins, ld);
+  hipLaunchKernelGGL(loudness_ragged_kernel, dim3(T, B), dim3(256), 0, st, spec, a_weight_db, frames, gmax_ws, out, T,
                      n_bins, ld, amin, top_db, add_eps);
   SRN_CHECK_LAUNCH();
   return 0;

@@ -6,11 +6,15 @@ CPU before the hot path.
     loudness_extract(audio, sampling_rate, hop_length)   serenade/bin/preprocess.py:126-137
 
 Same names, arguments and return shapes ((#frames, num_mels) and (#frames,)); `audio` may also be a (B, n) batch of
-equal-length signals, which adds a leading batch axis to the result.  Inputs are CUDA tensors (numpy arrays are
-uploaded); everything runs in libserenade_hip.so: the STFT is a strided implicit GEMM (`srn_conv_gemm`, exact-fp32
-MFMA) over the reflect-padded signal viewed as rows of 16 samples with window x DFT basis weights, followed by
-`srn_logmel` / `srn_loudness`.  The constant tables (window, DFT basis, Slaney mel filterbank, A-weighting) are
-built once on the host in float64.  There is no CPU path.
+equal-length signals, which adds a leading batch axis to the result.  With `lengths=` (B sample counts) the batch is a
+padded one of unequal utterances, as audio.prepare returns it: each item is padded, analysed and -- for the loudness
+floor -- normalised on its own, frames at or past an item's own 1 + n_b // hop are exactly 0 and the call returns
+(tensor, [frames per item]), the convention of ContentVec and TranscriptionModel.  Inputs are CUDA tensors (numpy arrays
+are uploaded); everything runs in libserenade_hip.so: the STFT is a strided implicit GEMM (`srn_conv_gemm`, exact-fp32
+MFMA) over the padded signal viewed as rows of 16 samples with window x DFT basis weights, followed by `srn_logmel` /
+`srn_loudness` (`srn_logmel_ragged` / `srn_loudness_ragged` with lengths).  The constant tables (window x DFT basis,
+Slaney mel filterbank, A-weighting) are built on the host in float64 once per process and device (`_table`), whatever
+(B, n) the plans that use them have.  There is no CPU path.
 
 Parity: librosa is not vendored by the reference and not installed here, so this row is pinned to the restatement
 in oracle/features_oracle.py only ("parity unpinned").
@@ -21,11 +25,12 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .plan import lru_get, require_cuda as _require_cuda, rup
+from .plan import item_lengths, lru_get, require_cuda as _require_cuda, rup
 
 __all__ = ["logmelfilterbank", "loudness_extract"]
 
 _PLANS = {}
+_TABLES = {}  # (device, what, what it depends on) -> device tensor: one copy per process, shared by every plan
 
 
 # ---------------------------------------------------------------------------------------------- constant tables
@@ -70,13 +75,35 @@ def _a_weight_db(freqs, min_db=-80.0):
     return np.maximum(min_db, w)
 
 
+def _table(dev, key, make):
+    """the per-process device copy of a constant table: built (host, float64 -> float32) on first use only"""
+    k = (str(dev),) + key
+    if k not in _TABLES:
+        _TABLES[k] = torch.from_numpy(np.ascontiguousarray(make(), dtype=np.float32)).to(dev)
+    return _TABLES[k]
+
+
+def _basis_table(dev, n_fft, win_length, n_pad):
+    return _table(dev, ("basis", n_fft, win_length, n_pad), lambda: _dft_basis(n_fft, win_length, n_pad))
+
+
+def _mel_table(dev, sr, n_fft, n_mels, fmin, fmax):
+    """(n_bins, n_mels): the filterbank transposed, as srn_logmel reads it"""
+    return _table(dev, ("mel", sr, n_fft, n_mels, fmin, fmax), lambda: _slaney_mel(sr, n_fft, n_mels, fmin, fmax).T)
+
+
+def _a_weight_table(dev, sr, n_bins):
+    return _table(dev, ("a_weight", sr, n_bins), lambda: _a_weight_db(np.linspace(0.0, sr / 2.0, n_bins)))
+
+
 # ---------------------------------------------------------------------------------------------- STFT plan
 class _Stft:
     """reflect pad + strided implicit-GEMM STFT of (B, n) signals -> self.spec (B, frames, ld) = [re | im | 0]"""
 
     def __init__(self, dev, B, n, n_fft, hop, win_length, pad_mode="reflect", lens=None, audio=None):
-        """lens: per-item sample counts (CUDA int32) -- each item is reflect-padded at its own end (srn_pad_ragged);
-        audio: a (B, n) buffer of the caller's to read the signal from, instead of one of the plan's own"""
+        """lens: per-item sample counts (CUDA int32) -- each item is padded at its own end (srn_pad_ragged mirrors
+        there, srn_pad_ragged_zero puts zeros); audio: a (B, n) buffer of the caller's to read the signal from, instead
+        of one of the plan's own"""
         if pad_mode not in ("reflect", "constant"):
             raise ValueError(f"pad_mode {pad_mode!r}: 'reflect' or 'constant'")
         c = math.gcd(math.gcd(n_fft, hop), 16)
@@ -91,14 +118,13 @@ class _Stft:
         f = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
         self.audio = f(B, n) if audio is None else audio
         self.sig, self.spec = f(B, self.ld_sig), f(B, self.frames, self.ld)
-        self.basis = torch.from_numpy(_dft_basis(n_fft, win_length, self.ld)).to(dev)
+        self.basis = _basis_table(dev, n_fft, win_length, self.ld)
         if lens is None:
             self.ops = [ops.CallOp("srn_pad_signal", (self.audio, self.sig, B, n, pad, self.ld_sig,
                                                       int(pad_mode == "constant")))]
         else:
-            if pad_mode != "reflect":
-                raise ValueError("per-item lengths need pad_mode 'reflect'")
-            self.ops = [ops.CallOp("srn_pad_ragged", (self.audio, n, lens, self.sig, B, n, pad, self.ld_sig))]
+            entry = "srn_pad_ragged" if pad_mode == "reflect" else "srn_pad_ragged_zero"
+            self.ops = [ops.CallOp(entry, (self.audio, n, lens, self.sig, B, n, pad, self.ld_sig))]
         # A frame is a contraction over n_fft samples = taps of `cw` samples each.  The signal is viewed as rows that START
         # every c samples (row stride c, so any frame start is a row) but are cw = 32 samples WIDE (overlapping rows are
         # fine for a read-only operand): 32-channel taps take the fast contraction kernel, 16-wide ones the generic one
@@ -128,9 +154,50 @@ def _as_batch(audio):
     return (a.unsqueeze(0), True) if a.dim() == 1 else (a, False)
 
 
+def _item_frames(lengths, B, n, hop, what, reflect_pad=None):
+    """the checked per-item sample counts of a padded (B, n) batch and their frame counts 1 + n_b // hop.
+    reflect_pad: the reflect padding each item must be longer than (numpy.pad's own condition, srn_pad_signal's check
+    for the dense call)."""
+    lens = item_lengths(lengths, B, n, what)
+    if reflect_pad is not None:
+        for b, v in enumerate(lens):
+            if v <= reflect_pad:
+                raise ValueError(f"{what}: item {b} has {v} samples, reflect padding of {reflect_pad} needs more")
+    return lens, [1 + v // hop for v in lens]
+
+
+class _Ragged:
+    """what a plan with per-item lengths adds: `counts` (2, B) device int32 = [samples | frames], refilled by every
+    call (the plan depends on (B, n) only, not on the lengths)"""
+
+    def __init__(self, dev, B):
+        self.counts = torch.zeros(2, B, device=dev, dtype=torch.int32)
+        self.samples, self.frames = self.counts[0], self.counts[1]
+
+    def load(self, lens, frames):
+        self.counts.copy_(torch.tensor([lens, frames], dtype=torch.int32))
+
+
+def _run(plan, a, lens, frames, single):
+    st, rg, out, ol = plan
+    st.load(a)
+    if rg is not None:
+        rg.load(lens, frames)
+    for op in ol:
+        op()
+    res = out.clone()
+    res = res[0] if single else res
+    return res if rg is None else (res, frames)
+
+
 def logmelfilterbank(audio, sampling_rate, fft_size=1024, hop_size=256, win_length=None, window="hann", num_mels=80,
-                     fmin=None, fmax=None, eps=1e-10, log_base=10.0):
-    """preprocess.py:140-203: (#frames, num_mels) log-mel spectrogram (leading batch axis for (B, n) input)."""
+                     fmin=None, fmax=None, eps=1e-10, log_base=10.0, lengths=None):
+    """preprocess.py:140-203: (#frames, num_mels) log-mel spectrogram (leading batch axis for (B, n) input).
+
+    lengths: the sample counts n_b of a padded (B, n) batch, each in (fft_size // 2, n].  The result is then
+    ((B, 1 + n // hop_size, num_mels), [1 + n_b // hop_size]): item b's own frames are what its B = 1 call on
+    audio[b, :n_b] computes, up to the fp32 summation order of the STFT (audio[b, n_b:] is never read), the frames
+    past them are 0."""
     if window != "hann":
         raise ValueError("only the recipe's Hann window is implemented")
     if log_base not in (None, 10.0, 2.0):
@@ -141,48 +208,64 @@ def logmelfilterbank(audio, sampling_rate, fft_size=1024, hop_size=256, win_leng
     fmin = 0 if fmin is None else fmin
     fmax = sampling_rate / 2 if fmax is None else fmax
     key = ("mel", str(a.device), B, n, sampling_rate, fft_size, hop_size, win_length, num_mels, fmin, fmax, eps, log_base)
+    lens = frames = None
+    if lengths is not None:
+        lens, frames = _item_frames(lengths, B, n, hop_size, "logmelfilterbank", reflect_pad=fft_size // 2)
+        key += ("ragged",)
 
     def make():
-        st = _Stft(a.device, B, n, fft_size, hop_size, win_length)
-        mel_t = torch.from_numpy(_slaney_mel(sampling_rate, fft_size, num_mels, fmin, fmax).T.astype(np.float32).copy())
-        mel_t = mel_t.to(a.device).contiguous()
+        rg = None if lengths is None else _Ragged(a.device, B)
+        st = _Stft(a.device, B, n, fft_size, hop_size, win_length, lens=None if rg is None else rg.samples)
+        mel_t = _mel_table(a.device, sampling_rate, fft_size, num_mels, fmin, fmax)
         out = torch.zeros(B, st.frames, num_mels, device=a.device, dtype=torch.float32)
         mode = 0 if log_base is None else int(log_base)
-        op = ops.CallOp("srn_logmel", (st.spec, mel_t, out, B * st.frames, st.nb, st.ld, num_mels, float(eps), mode))
-        return st, mel_t, out, st.ops + [op]
+        if rg is None:
+            op = ops.CallOp("srn_logmel", (st.spec, mel_t, out, B * st.frames, st.nb, st.ld, num_mels, float(eps),
+                                           mode))
+        else:
+            op = ops.CallOp("srn_logmel_ragged", (st.spec, mel_t, rg.frames, out, B, st.frames, st.nb, st.ld, num_mels,
+                                                  float(eps), mode))
+        return st, rg, out, st.ops + [op]
 
-    st, _, out, ol = lru_get(_PLANS, key, 8, make)
-    st.load(a)
-    for op in ol:
-        op()
-    res = out.clone()
-    return res[0] if single else res
+    return _run(lru_get(_PLANS, key, 8, make), a, lens, frames, single)
 
 
-def loudness_extract(audio, sampling_rate, hop_length, pad_mode="constant"):
+def loudness_extract(audio, sampling_rate, hop_length, pad_mode="constant", lengths=None):
     """preprocess.py:126-137: (#frames,) log mean A-weighted amplitude (librosa defaults: n_fft 2048, Hann,
     power_to_db top_db 80 relative to the utterance's loudest bin).
 
     pad_mode: the reference calls `librosa.stft(audio, hop_length=hop_length)` without a pad_mode, so the edge frames
     depend on the installed librosa: "constant" (zeros) since librosa 0.10 -- the default here --, "reflect" before
     (setup.cfg only asks for librosa >= 0.8.0).  Use the mode the `lft` features of a checkpoint were extracted with;
-    about n_fft / 2 / hop frames at each end of an utterance differ between the two."""
+    about n_fft / 2 / hop frames at each end of an utterance differ between the two.
+
+    lengths: the sample counts n_b of a padded (B, n) batch, each in [1, n] ((1024, n] with pad_mode "reflect").  The
+    result is then ((B, 1 + n // hop_length), [1 + n_b // hop_length]): item b's own frames are what its B = 1 call
+    on audio[b, :n_b] computes, up to the fp32 summation order of the STFT -- the top_db floor is relative to the
+    item's own loudest bin, audio[b, n_b:] is never read --, the frames past them are 0."""
     n_fft = 2048
+    if pad_mode not in ("reflect", "constant"):
+        raise ValueError(f"pad_mode {pad_mode!r}: 'reflect' or 'constant'")
     a, single = _as_batch(audio)
     B, n = a.shape
     key = ("loud", str(a.device), B, n, sampling_rate, hop_length, pad_mode)
+    lens = frames = None
+    if lengths is not None:
+        lens, frames = _item_frames(lengths, B, n, hop_length, "loudness_extract",
+                                    reflect_pad=n_fft // 2 if pad_mode == "reflect" else None)
+        key += ("ragged",)
 
     def make():
-        st = _Stft(a.device, B, n, n_fft, hop_length, n_fft, pad_mode)
-        aw = torch.from_numpy(_a_weight_db(np.linspace(0.0, sampling_rate / 2.0, st.nb)).astype(np.float32)).to(a.device)
+        rg = None if lengths is None else _Ragged(a.device, B)
+        st = _Stft(a.device, B, n, n_fft, hop_length, n_fft, pad_mode, lens=None if rg is None else rg.samples)
+        aw = _a_weight_table(a.device, sampling_rate, st.nb)
         ws = torch.zeros(B, device=a.device, dtype=torch.int32)
         out = torch.zeros(B, st.frames, device=a.device, dtype=torch.float32)
-        op = ops.CallOp("srn_loudness", (st.spec, aw, ws, out, B, st.frames, st.nb, st.ld, 1e-10, 80.0, 1e-5))
-        return st, (aw, ws), out, st.ops + [op]
+        if rg is None:
+            op = ops.CallOp("srn_loudness", (st.spec, aw, ws, out, B, st.frames, st.nb, st.ld, 1e-10, 80.0, 1e-5))
+        else:
+            op = ops.CallOp("srn_loudness_ragged", (st.spec, aw, rg.frames, ws, out, B, st.frames, st.nb, st.ld, 1e-10,
+                                                    80.0, 1e-5))
+        return st, rg, out, st.ops + [op]  # (the op pins ws)
 
-    st, _, out, ol = lru_get(_PLANS, key, 8, make)
-    st.load(a)
-    for op in ol:
-        op()
-    res = out.clone()
-    return res[0] if single else res
+    return _run(lru_get(_PLANS, key, 8, make), a, lens, frames, single)

@@ -1,15 +1,17 @@
 """From raw waveforms to the tracks of a preprocessing dump in one call: the loop body of
 serenade/bin/preprocess.py:399-611 without ground-truth MIDI (`--skip_gtmidi`), on the GPU.
 
-    extract_features(audio, fs, config, contentvec, transcriber, midi_config, f0_range=(70, 1100), lengths=None)
+    extract_features(audio, fs, config, contentvec, transcriber, midi_config, f0_range=(70, 1100), lengths=None,
+                     ragged=False)
         -> one dict per utterance {"wave", "hubert", "logmel", "loud", "gt_lf0_score", "est_lf0_score", "f0", "vuv",
            "midi"} of numpy float32 arrays, or None where the reference skips the utterance
 
 Nothing is computed here: audio.prepare, features.logmelfilterbank / loudness_extract, world.extract_f0 (Harvest),
 ContentVec, the transcriber with reference_f0 (pYIN), FramewiseDecoder and estimate_score are composed as the
-reference composes them.  The ragged front-ends take the whole batch; logmelfilterbank and loudness_extract are not
-ragged and run once per group of utterances of equal length.  The csv / json / yaml handling of the reference's main()
-and the hdf5 writing stay with the caller (utils.io.write_hdf5 takes every track as it is returned)."""
+reference composes them.  The ragged front-ends take the whole batch; logmelfilterbank and loudness_extract run once
+per group of utterances of equal length by default, and once for the whole batch (`lengths=`) with ragged=True.  The
+csv / json / yaml handling of the reference's main() and the hdf5 writing stay with the caller (utils.io.write_hdf5
+takes every track as it is returned)."""
 import numpy as np
 import torch
 
@@ -29,12 +31,19 @@ def _f32(t):
 
 
 @torch.no_grad()
-def extract_features(audio, fs, config, contentvec, transcriber, midi_config, f0_range=(70, 1100), lengths=None):
+def extract_features(audio, fs, config, contentvec, transcriber, midi_config, f0_range=(70, 1100), lengths=None,
+                     ragged=False):
     """audio, fs, lengths: as audio.prepare takes them (a list of utterances or a padded batch; one rate or one per
     item).  config: the recipe's preprocessing config (sampling_rate, trim_*, fft_size, hop_size, win_length, window,
     num_mels, fmin, fmax, shiftms, optional log_base).  contentvec: a loaded ContentVec; transcriber: a loaded
     TranscriptionModel and midi_config its checkpoint's config.  f0_range: (minf0, maxf0) of Harvest, scalars or one
     value per item (preprocess.py:474-483 reads them from a per-speaker file; 70 / 1100 is its fallback).
+    ragged: False runs log-mel and loudness once per group of utterances of equal sample count -- after the silence
+    trim that is one B = 1 call, with a plan of its own, per utterance; True runs each once for the whole batch with
+    per-item lengths.  Every item is still padded, analysed and floored on its own, but srn_conv_gemm decides split-K
+    per launch shape, so the STFT of an item inside a batch is not promised to round like its B = 1 call of another
+    shape: `logmel` and `loud` agree between the two settings to the fp32 rounding of the STFT (tested to 2e-4, the
+    bound of both functions against their float64 restatement), not bit for bit.  The other tracks are the same bits.
 
     Per item, the tracks preprocess.py:567-611 writes, every one float32 and cropped to
     min(len(loud), len(midi), len(hubert)) frames T except the wave: wave (n,), hubert (T, hidden), logmel
@@ -45,17 +54,24 @@ def extract_features(audio, fs, config, contentvec, transcriber, midi_config, f0
     sr = config["sampling_rate"]
     x, lens, x16, lens16 = A.prepare(audio, fs, config, lengths)
     B = len(lens)
-    # log-mel and loudness: one call per group of equal length (preprocess.py:435-447, :471-472)
+    # log-mel and loudness (preprocess.py:435-447, :471-472): one call per group of equal length, or one ragged call
+    kw = dict(sampling_rate=sr, hop_size=config["hop_size"], fft_size=config["fft_size"],
+              win_length=config["win_length"], window=config["window"], num_mels=config["num_mels"],
+              fmin=config["fmin"], fmax=config["fmax"], log_base=config.get("log_base", 10.0))
     logmel, loud = [None] * B, [None] * B
-    for n in sorted(set(lens)):
-        idx = [b for b in range(B) if lens[b] == n]
-        xs = x[idx, :n]
-        mel = logmelfilterbank(xs, sampling_rate=sr, hop_size=config["hop_size"], fft_size=config["fft_size"],
-                               win_length=config["win_length"], window=config["window"], num_mels=config["num_mels"],
-                               fmin=config["fmin"], fmax=config["fmax"], log_base=config.get("log_base", 10.0))
-        ld = loudness_extract(xs, sr, config["hop_size"])
-        for i, b in enumerate(idx):
-            logmel[b], loud[b] = mel[i], ld[i][:, None]
+    if ragged:
+        mel, fr = logmelfilterbank(x, lengths=lens, **kw)
+        ld, _ = loudness_extract(x, sr, config["hop_size"], lengths=lens)
+        for b in range(B):
+            logmel[b], loud[b] = mel[b, :fr[b]], ld[b, :fr[b], None]
+    else:
+        for n in sorted(set(lens)):
+            idx = [b for b in range(B) if lens[b] == n]
+            xs = x[idx, :n]
+            mel = logmelfilterbank(xs, **kw)
+            ld = loudness_extract(xs, sr, config["hop_size"])
+            for i, b in enumerate(idx):
+                logmel[b], loud[b] = mel[i], ld[i][:, None]
     # Harvest (:485-493)
     f0s = world.extract_f0(x, sr, f0_range[0], f0_range[1], config["shiftms"], lengths=lens)
     # ContentVec at the acoustic frame shift (:495-503) and the transcriber's logits and pYIN contours (:505-507)
