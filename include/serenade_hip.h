@@ -800,6 +800,36 @@ int srn_col_moments(const float* x, const int64_t* row_off, int64_t R, double* s
 int srn_scale_collate(const float* x, const int64_t* row_off, int64_t R, const int32_t* order, const void* sub,
                       const void* div, int wide, float* out, int Tmax, int B, int Bout, int C, void* stream);
 
+/*
+ * The host loop behind the note transcriber (serenade_amd/transcriber.py drives both, tests/_notes_ref.py is the
+ * restatement; notes.hip states the semantics once).  Ragged batches: padded arrays plus per-item counts, clamped
+ * against the padded extents passed alongside; one workgroup per item, so an item inside a batch gets the bits of its
+ * own B = 1 call.
+ */
+#define SRN_NOTE_MAX_FRAMES 8192 /* frames per item (Tmax) of srn_note_decode; the host raises beyond it */
+/* serenade/modules/phoneme_midi/decoding.py:22-159 (FramewiseDecoder.decode with f0 given, _peak_selector,
+ * _decode_notes): logits (B, Tmax, 3) float32 contiguous (onset, offset, frame), frames (B) valid frames per item;
+ * f0 (B, Fmax) float64 pYIN contour in Hz (NaN = unvoiced), f0_frames (B) its frames per item; pitch_sum 0 median,
+ * 1 weighted_mean, 2 weighted_median; log2_a4 = log2(440) as the host computes it.  Out: counts (B) notes per item,
+ * intervals (B, Tmax, 2) int32 (onset, offset + 1), pitches (B, Tmax) float64 MIDI pitch per note; entries past an
+ * item's count are 0.  Scratch: ws_f (B, 5, Tmax) float32, ws_d (B, 4, Tmax) float64, ws_i (B, 2, Tmax) int32. */
+int srn_note_decode(const float* logits, const int32_t* frames, const double* f0, const int32_t* f0_frames, int B,
+                    int Tmax, int Fmax, float onset_threshold, float offset_threshold, int pitch_sum, double log2_a4,
+                    float* ws_f, double* ws_d, int32_t* ws_i, int32_t* counts, int32_t* intervals, double* pitches,
+                    void* stream);
+/* serenade/bin/preprocess.py:237-259 (midi_to_frames), :117-123 (_midi_to_hz(log_f0=True)) and the arithmetic of
+ * :510-528: counts (B), intervals (B, cap, 2) int32 >= 0 and pitches (B, cap) float64 as srn_note_decode leaves them;
+ * n_samples (B) samples per item at the acoustic rate; scale = hop_length / sample_rate of the transcriber,
+ * shift = shiftms / 1000, sampling_rate the acoustic rate, all float64 from the host; table (128) int32 the log-Hz
+ * value per MIDI number.  Per item n = ceil((n_samples / sampling_rate) / shift) frames (clamped to Nmax, written to
+ * n_frames (B)); note k covers the frames floor((onset scale) / shift) .. min(ceil((end scale) / shift), n) with its
+ * pitch rounded half to even, the last note covering a frame wins, frames of no note are 0: midi (B, Nmax) int32 and
+ * lf0 (B, Nmax) int32 = table[midi]; every element is written.  bad (1) int32 is set when a rounded pitch lies
+ * outside 0 .. 127 or an interval is negative (such a note is left out).  Scratch: ws (B, cap, 3) int32. */
+int srn_note_frames(const int32_t* counts, const int32_t* intervals, const double* pitches, int B, int cap,
+                    const int32_t* n_samples, double scale, double shift, double sampling_rate, const int32_t* table,
+                    int32_t* ws, int32_t* midi, int32_t* lf0, int Nmax, int32_t* n_frames, int32_t* bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

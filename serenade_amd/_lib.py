@@ -207,6 +207,8 @@ _SIGS = {
     "srn_wave_window": (c_int, [_P, c_int, c_int64, _P, _P, c_int, _P, c_int64, c_int, c_int, _P]),
     "srn_col_moments": (c_int, [_P, _P, c_int64] + [_P] * 5 + [c_int, c_int, _P]),
     "srn_scale_collate": (c_int, [_P, _P, c_int64, _P, _P, _P, c_int, _P] + [c_int] * 4 + [_P]),
+    "srn_note_decode": (c_int, [_P] * 4 + [c_int] * 3 + [c_float] * 2 + [c_int, c_double] + [_P] * 7),
+    "srn_note_frames": (c_int, [_P] * 3 + [c_int] * 2 + [_P] + [c_double] * 3 + [_P] * 4 + [c_int] + [_P] * 3),
 }
 
 EXPORTS = tuple(_SIGS)

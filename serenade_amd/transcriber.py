@@ -9,9 +9,13 @@ FramewiseDecoder (decoding.py) on the host.
       .forward(wave16k, lengths)        (B, T, 3) onset / offset / activation logits of every item on its own
       .frames(n_samples)                T = 1 + n // hop_length
     FramewiseDecoder(config).decode(logits_item, f0)      decoding.py, on the host
+      .decode_batch(logits, frames, f0, f0_frames)        the same for a ragged batch in one launch on the GPU
+                                                          (srn_note_decode): (counts, intervals, pitches) tensors
     reference_f0(wave16k, lengths, config)                decoding.py:36-45's librosa.pyin call, on the GPU
                                                           (pitch.pyin): one f0 contour per item for decode(f0=...)
+    reference_f0_device(wave16k, lengths, config)         the same contours left on the GPU for decode_batch
     estimate_score(pitches, intervals, n_samples, ...)    preprocess.py:510-528: (midi frames, est_lf0_score)
+    estimate_score_batch(counts, intervals, pitches, ...) the same for a ragged batch on the GPU (srn_note_frames)
 
 The network, per item (B = 1, eval mode):
     pitch = DilatedConvStack(dB-mel(x)) -> BiLSTM                          (pitch_conv_stack, pitch_rnn)
@@ -45,9 +49,10 @@ import torch
 from . import _lib, ops, pitch
 from .features import _slaney_mel, _Stft
 from .ops import ConvOp, GraphRunner
-from .plan import check_state, linear_op, lru_get, rup, wave_batch
+from .plan import check_state, dev_i32, linear_op, lru_get, rup, wave_batch
 
-__all__ = ["TranscriptionModel", "FramewiseDecoder", "estimate_score", "reference_f0", "DEFAULT_CONFIG"]
+__all__ = ["TranscriptionModel", "FramewiseDecoder", "estimate_score", "estimate_score_batch", "reference_f0",
+           "reference_f0_device", "DEFAULT_CONFIG", "NOTE_MAX_FRAMES"]
 
 # ASSUMED geometry: no transcriber checkpoint is available to read ckpt["config"] from.  The front-end follows the
 # reference's 16 kHz input (preprocess.py:495,506); model_complexity 48 (model_size 768, LSTM hidden 384) and the
@@ -58,6 +63,8 @@ DEFAULT_CONFIG = dict(
     lang_model_config=dict(_FRONT, model_complexity=48, num_lbl=40),
 )
 N_PHONEMES = 39  # PhonemeRecognitionModel.output_features
+NOTE_MAX_FRAMES = 8192  # SRN_NOTE_MAX_FRAMES of serenade_hip.h: frames per item of decode_batch
+PITCH_SUM = {"median": 0, "weighted_mean": 1, "weighted_median": 2}  # srn_note_decode's pitch_sum
 TOP_DB, AMIN, BN_EPS = 80.0, 1e-10, 1e-5
 _CONVS = ((0, 1), (3, 4), (8, 9))  # (conv, BatchNorm) indices inside a stack's nn.Sequential
 
@@ -417,6 +424,39 @@ class FramewiseDecoder:
         f0 = torch.as_tensor(np.asarray(f0.detach().cpu() if isinstance(f0, torch.Tensor) else f0)).float()
         return self._notes(_peaks(on, self.onset_threshold), f0, _peaks(off, self.offset_threshold), frames)
 
+    @torch.no_grad()
+    def decode_batch(self, logits, frames, f0, f0_frames):
+        """decode() of every item of a ragged batch in one launch (srn_note_decode; notes.hip states the semantics).
+        logits (B, Tmax, 3) float32 on the GPU with `frames` valid frames per item, as TranscriptionModel.forward
+        returns them; f0 (B, Fmax) float64 on the GPU with `f0_frames` frames per item, as pitch.pyin and
+        reference_f0_device return them.  Returns device tensors: counts (B,) int32 notes per item, intervals
+        (B, Tmax, 2) int32 [onset frame, offset frame + 1] and pitches (B, Tmax) float64, zeros past an item's count.
+        The arithmetic from the contour on is float64 (decode() follows the reference's float32), and the sigmoid is
+        the GPU's: decisions agree with decode() wherever no activation lies within an fp32 rounding of a threshold
+        or of another activation.  An item may have at most NOTE_MAX_FRAMES frames: ValueError beyond, no truncation."""
+        _require_cuda(logits, "decode_batch: logits")
+        if not (logits.dtype == torch.float32 and logits.ndim == 3 and logits.shape[2] == 3):
+            raise RuntimeError("decode_batch: logits must be a (B, Tmax, 3) float32 tensor")
+        if not (isinstance(f0, torch.Tensor) and f0.device == logits.device and f0.dtype == torch.float64
+                and f0.ndim == 2 and f0.shape[0] == logits.shape[0]):
+            raise RuntimeError("decode_batch: f0 must be a (B, Fmax) float64 tensor on the logits' device")
+        B, Tmax, _ = logits.shape
+        Fmax = f0.shape[1]
+        nt, nf = _counts(frames, B, Tmax, "frames"), _counts(f0_frames, B, Fmax, "f0_frames")
+        if B == 0 or Tmax == 0 or Fmax == 0:
+            raise ValueError(f"decode_batch: empty batch (logits {tuple(logits.shape)}, f0 {tuple(f0.shape)})")
+        if Tmax > NOTE_MAX_FRAMES:
+            raise ValueError(f"decode_batch: {Tmax} frames per item exceed the kernel's limit of {NOTE_MAX_FRAMES}")
+        dev = logits.device
+        e = lambda *shape, dtype: torch.empty(*shape, dtype=dtype, device=dev)
+        counts, intervals = e(B, dtype=torch.int32), e(B, Tmax, 2, dtype=torch.int32)
+        pitches = e(B, Tmax, dtype=torch.float64)
+        ops.call("srn_note_decode", logits.contiguous(), dev_i32(nt, dev), f0.contiguous(), dev_i32(nf, dev), B, Tmax,
+                 Fmax, float(self.onset_threshold), float(self.offset_threshold), PITCH_SUM[self.pitch_sum],
+                 float(np.log2(440.0)), e(B, 5, Tmax, dtype=torch.float32), e(B, 4, Tmax, dtype=torch.float64),
+                 e(B, 2, Tmax, dtype=torch.int32), counts, intervals, pitches)
+        return counts, intervals, pitches
+
     def _notes(self, onsets, f0, offsets, frames):
         midi = torch.from_numpy(_hz_to_midi(f0).squeeze())
         on_idx = [int(i) for i in _rises(onsets).nonzero()[:, 0]]
@@ -477,6 +517,31 @@ def reference_f0(wave16k, lengths=None, config=None):
     return [f0[b, :int(n)].copy() for b, n in enumerate(frames)]
 
 
+def reference_f0_device(wave16k, lengths=None, config=None):
+    """reference_f0 without the visit to the host: (f0 (B, T) float64 on the GPU, NaN where unvoiced and past an
+    item's frames; frames per item as a list), ready for FramewiseDecoder.decode_batch"""
+    cfg = DEFAULT_CONFIG if config is None else config
+    x = wave16k.reshape(1, -1) if wave16k.ndim == 1 else wave16k
+    f0, _, _, frames = pitch.pyin(x, lengths, fmin=65, fmax=2093, sr=cfg["sample_rate"],
+                                  frame_length=cfg["win_length"], hop_length=cfg["hop_length"], fill_na=np.nan,
+                                  center=True)
+    return f0, [int(n) for n in frames]
+
+
+def _require_cuda(t, what):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise RuntimeError(f"{what} must be a CUDA (ROCm) tensor; there is no CPU path (decode / estimate_score are "
+                           "the host forms)")
+
+
+def _counts(values, B, limit, what):
+    """B per-item counts in [0, limit] as a list of ints"""
+    v = [int(n) for n in (values.tolist() if hasattr(values, "tolist") else values)]
+    if len(v) != B or (B and (min(v) < 0 or max(v) > limit)):
+        raise ValueError(f"{what} {v} must give {B} counts in [0, {limit}]")
+    return v
+
+
 def midi_to_frames(midi_values, time_intervals, T, shift_ms=10):
     """preprocess.py midi_to_frames: notes (pitch, [start s, end s]) on a frame grid of shift_ms, ceil(T / shift) frames,
     floor(start / shift) .. ceil(end / shift) (clipped), later notes overwriting earlier ones; int32"""
@@ -509,3 +574,40 @@ def estimate_score(pitches, intervals, n_samples, config=None, sampling_rate=240
     midi = np.array([round(p) for p in pitches])
     midi = midi_to_frames(midi, time, n_samples / sampling_rate, shift_ms=shiftms)
     return midi, np.expand_dims(midi_to_log_hz(midi), axis=-1)
+
+
+@torch.no_grad()
+def estimate_score_batch(counts, intervals, pitches, n_samples, config=None, sampling_rate=24000, shiftms=10):
+    """estimate_score of every item of a ragged batch in one launch (srn_note_frames).  counts (B,) int32, intervals
+    (B, cap, 2) int32 and pitches (B, cap) float64 on the GPU, as decode_batch returns them (or any caller-supplied
+    notes of that layout); n_samples: samples per item at `sampling_rate`.  Returns (midi (B, Nmax) int32,
+    est_lf0_score (B, Nmax) int32, frames per item as a list): item b holds its track in [:frames[b]] and zeros
+    behind, bit for bit estimate_score's (the two IEEE operations of every frame index are numpy's, in its order, and
+    the log-Hz value per MIDI number is midi_to_log_hz's own).  ValueError when a rounded pitch lies outside 0..127."""
+    cfg = DEFAULT_CONFIG if config is None else config
+    _require_cuda(counts, "estimate_score_batch: counts")
+    if not (counts.dtype == torch.int32 and counts.ndim == 1):
+        raise RuntimeError("estimate_score_batch: counts must be a (B,) int32 tensor")
+    B, dev = counts.shape[0], counts.device
+    if not (intervals.dtype == torch.int32 and intervals.ndim == 3 and intervals.shape[0] == B
+            and intervals.shape[2] == 2 and pitches.dtype == torch.float64
+            and tuple(pitches.shape) == tuple(intervals.shape[:2]) and intervals.device == dev == pitches.device):
+        raise RuntimeError("estimate_score_batch: intervals (B, cap, 2) int32 and pitches (B, cap) float64 on the "
+                           "device of counts are needed")
+    cap = intervals.shape[1]
+    ns = _counts(n_samples, B, 2 ** 31 - 1, "estimate_score_batch: n_samples")
+    if B == 0 or cap == 0:
+        raise ValueError("estimate_score_batch: empty batch")
+    scale, shift = cfg["hop_length"] / cfg["sample_rate"], shiftms / 1000.0
+    frames = [int(np.ceil((n / sampling_rate) / shift)) for n in ns]
+    Nmax = max(max(frames), 1)
+    table = midi_to_log_hz(np.arange(128, dtype=np.int32))
+    e = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    midi, lf0, n_frames, bad = e(B, Nmax), e(B, Nmax), e(B), e(1)
+    ops.call("srn_note_frames", counts, intervals.contiguous(), pitches.contiguous(), B, cap, dev_i32(ns, dev),
+             float(scale), float(shift), float(sampling_rate), dev_i32(table, dev), e(B, cap, 3), midi, lf0, Nmax,
+             n_frames, bad)
+    if int(bad.item()):
+        raise ValueError("estimate_score_batch: a note's rounded pitch lies outside the MIDI numbers 0..127 (or an "
+                         "interval is negative)")
+    return midi, lf0, frames
