@@ -191,6 +191,9 @@ def d4c_love_train(x, fs, f0, position):
     b0 = int(np.ceil(100.0 * fft_size / fs))
     b1 = int(np.ceil(4000.0 * fft_size / fs))
     b2 = int(np.ceil(7900.0 * fft_size / fs))
+    # WORLD itself reads past its spectrum when 7.9 kHz (or 4 kHz) lies above Nyquist, i.e. for fs < 15.8 kHz, so what
+    # happens there is this project's choice, stated here once: both limits stop at Nyquist, as the kernel's do.
+    b1, b2 = min(b1, fft_size // 2), min(b2, fft_size // 2)
     cur = max(f0, lowest_f0)
     wav = _d4c_windowed(x, fs, cur, position, "blackman", 3.0)
     spec = np.fft.rfft(wav, fft_size)
@@ -402,7 +405,7 @@ def analyze(x, lf0, fs=24000, frame_period=5.0, mcep_dim=39, alpha=0.466,
             dense_factors=(0.5, 1, 4, 8), upsample_scales=(5, 4, 3, 2), mean=None, scale=None):
     """x float64 waveform, lf0 the decode CLI's contour -> dict(c (T, 43), cf0, uv, dfs [4], ok)."""
     t = harvest_time_axis(len(x), fs, frame_period)
-    f0 = match_length(lf0, len(t))
+    f0 = np.atleast_1d(match_length(lf0, len(t)))  # a contour of one frame comes back 0-d from the squeeze
     mcep = freqt_from_cepstrum(cheaptrick(x, f0, t, fs, want="cepstrum"), mcep_dim, alpha)
     bap = d4c_band_aperiodicity(x, f0, t, fs)
     uv, cf0, ok = convert_continuos_f0(f0)

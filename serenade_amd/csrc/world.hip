@@ -24,7 +24,7 @@ namespace {
 constexpr int NT_CHEAPTRICK = 256, NT_D4C = 512 /* at N = 2048; N / 4 in general */, NT_F0 = 256;
 constexpr double kPi = 3.14159265358979323846;
 constexpr double kSafeGuard = 1e-12;                        // world::kMySafeGuardMinimum
-constexpr double kNoiseAfterSmoothing = 1.7716279188122702e-16;  // world::kEps * sqrt(2 / pi): E|randn| * eps
+constexpr double kNoiseAfterSmoothing = 1.7716596207925437e-16;  // world::kEps * sqrt(2 / pi): E|randn| * eps
 
 __device__ __forceinline__ int mround(double x) { return x > 0 ? (int)(x + 0.5) : (int)(x - 0.5); }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -663,7 +663,8 @@ __global__ void f0_match_length_kernel(const double* __restrict__ in, int64_t in
 }
 
 // convert_continuos_f0 (ssc_postprocessing.py:51-72): hold the first / last voiced value outwards, join voiced frames
-// linearly (scipy interp1d: slope * (x - x_lo) + y_lo with x_lo the last voiced frame strictly before x).
+// linearly (scipy interp1d hands a 1-D float64 contour to np.interp: a frame that is a node keeps its value exactly,
+// any other gets slope * (x - x_lo) + y_lo with x_lo the last voiced frame before x).
 // One workgroup per item; ok[b] = 0 when every frame is unvoiced (cf0 = f0 then).
 __global__ __launch_bounds__(NT_F0) void cont_f0_kernel(const double* __restrict__ f0, int64_t bs,
                                                      const int* __restrict__ n_frames, double* __restrict__ cf0,
@@ -705,12 +706,12 @@ __global__ __launch_bounds__(NT_F0) void cont_f0_kernel(const double* __restrict
   auto value = [&](int j) { return j < first ? y[first] : (j >= last ? y[last] : y[j]); };
   for (int i = threadIdx.x; i < n; i += NT_F0) {
     double v;
-    if (n < 2) {
+    if (is_node(i)) {  // every frame of a contour of one or two frames is one
       v = value(i);
-    } else {
-      int lo = i > 0 ? i - 1 : 0;  // scipy: searchsorted(nodes, i) clipped to [1, len - 1], lo = that - 1
+    } else {  // first < i < last: a node on either side
+      int lo = i - 1;
       while (!is_node(lo)) --lo;
-      int hi = i > 0 ? i : 1;
+      int hi = i + 1;
       while (!is_node(hi)) ++hi;
       const double y_lo = value(lo), y_hi = value(hi);
       const double slope = (y_hi - y_lo) / (double)(hi - lo);

@@ -159,8 +159,9 @@ def _cheaptrick_raw(x, x_len, f0, t, n_frames, fs, q1, f0_floor, fft_size, want_
     B, F = f0.shape
     nb = fft_size // 2 + 1
     del f0_floor  # pyworld's argument only sizes the transform
-    sp = torch.empty(B, F, nb, dtype=_F64, device=dev) if want_sp else None
-    ceps = torch.empty(B, F, nb, dtype=_F64, device=dev) if want_ceps else None
+    # zeros, not empty: the frame kernels leave the rows past an item's n_frames unwritten (a ragged batch)
+    sp = torch.zeros(B, F, nb, dtype=_F64, device=dev) if want_sp else None
+    ceps = torch.zeros(B, F, nb, dtype=_F64, device=dev) if want_ceps else None
     # f0_floor: GetF0FloorForCheapTrick, the lowest F0 the window still fits
     _world_op("srn_world_cheaptrick", x, x_len, f0, t, n_frames, fs, fft_size, q1=q1,
               f0_floor=3.0 * fs / (fft_size - 3.0), out0=sp, out1=ceps)()
@@ -186,7 +187,7 @@ def _d4c_raw(x, x_len, f0, t, n_frames, fs, threshold):
     N = _d4c_fft_size(fs)
     nb = _n_bands(fs)
     wl = int(3000.0 * N / fs) * 2 + 1
-    bap = torch.empty(B, F, nb, dtype=_F64, device=dev)
+    bap = torch.zeros(B, F, nb, dtype=_F64, device=dev)  # rows past an item's n_frames stay unwritten
     _world_op("srn_world_d4c", x, x_len, f0, t, n_frames, fs, N, threshold=threshold, band_window=_nuttall(dev, wl),
               n_bands=nb, out0=bap)()
     return bap
@@ -284,7 +285,10 @@ class Analyzer:
     def features(self, wave, lengths, f0_list):
         """wave (B, N) float32 CUDA (converted audio), lengths (B,) valid samples, f0_list: B contours (the `lf0`
         datasets of the decode CLI).  Returns dict(c (B, 43, F) float32, mcep, bap (float64), f0, cf0 (B, F) float64,
-        uv, ok (B,) int32, n_frames list)."""
+        uv, ok (B,) int32, n_frames list).  In a ragged batch every track is exactly zero past its item's frames: the
+        cepstrum and aperiodicity buffers are zero-filled before the frame kernels run (one fill each per call), which
+        skip those frames, so the projection and the packer, which run over all B * F rows, only ever see zeros there;
+        with a scaler the packed zeros are -mean / scale, and those rows of `c` are filled with zeros again."""
         _require_cuda(wave, "wave")
         dev = wave.device
         wave = wave.to(torch.float32).reshape(len(f0_list), -1).contiguous()
@@ -309,6 +313,8 @@ class Analyzer:
         if self._stats is not None:
             mean, scale = (_table(dev, ("stats", i, self._stats[i].tobytes()), lambda i=i: self._stats[i]) for i in (0, 1))
         ops.call("srn_world_pack_features", mcep, mcep.size(-1), bap, bap.size(-1), mean, scale, c, B * F, nc)
+        if mean is not None and min(n_frames) < F:  # the zero rows past an item's frames came out as -mean / scale
+            c.masked_fill_((torch.arange(F, device=dev)[None] >= nf[:, None])[..., None], 0.0)
         uv, cf0, ok = _cont_f0_raw(f0, nf)
         return dict(c=c.transpose(1, 2), mcep=mcep, bap=bap, f0=f0, cf0=cf0, uv=uv, ok=ok, n_frames=n_frames, nf=nf)
 
