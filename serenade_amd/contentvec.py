@@ -130,6 +130,15 @@ class ContentVec:
         torch's own _weight_norm (bit-equal to the parametrized conv.weight)"""
         return torch._weight_norm(v.to(torch.float32), g.to(torch.float32), 2)
 
+    @staticmethod
+    def pack_pos_weight(pw, groups):
+        """grouped Conv1d weight (D, D / groups, K) -> srn_posconv_gelu_res's [g][tap][c in][n out], the output columns
+        zero-padded to whole 32-column blocks (32 up to 32 channels per group, else 64)"""
+        D, Cg, K = pw.shape
+        packed = torch.zeros(groups, K, Cg, 32 if Cg <= 32 else 64)
+        packed[..., :Cg] = pw.reshape(groups, Cg, Cg, K).permute(0, 3, 2, 1)
+        return packed
+
     def load_state_dict(self, sd):
         s = self.map_state_dict(sd)
         want = self.state_shapes()
@@ -147,11 +156,7 @@ class ContentVec:
              "fp_w": d(s["feature_projection.projection.weight"]), "fp_b": d(s["feature_projection.projection.bias"]),
              "enc_ln_w": d(s["encoder.layer_norm.weight"]), "enc_ln_b": d(s["encoder.layer_norm.bias"])}
         pw = self.fold_pos_weight(s["encoder.pos_conv_embed.conv.weight_g"], s["encoder.pos_conv_embed.conv.weight_v"])
-        Cg = D // G
-        npad = 32 if Cg <= 32 else 64
-        packed = torch.zeros(G, K, Cg, npad)
-        packed[..., :Cg] = pw.reshape(G, Cg, Cg, K).permute(0, 3, 2, 1)  # [g][tap][c in][n out]
-        w["pos_w"], w["pos_b"] = d(packed), d(s["encoder.pos_conv_embed.conv.bias"])
+        w["pos_w"], w["pos_b"] = d(self.pack_pos_weight(pw, G)), d(s["encoder.pos_conv_embed.conv.bias"])
         layers = []
         for i in range(c["num_hidden_layers"]):
             p = f"encoder.layers.{i}."

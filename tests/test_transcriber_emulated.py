@@ -32,9 +32,11 @@ def emul_transcriber(name, a):
         sv, ov = _tview(spec, B, T, ld_spec, T * ld_spec), _tview(out, B, T, ld_out, T * ld_out)
         for b in range(B):
             L = min(int(lens[b]), T)
-            p = sv[b, :L, :nb] ** 2 + sv[b, :L, nb:2 * nb] ** 2
-            db = 10 * torch.log10(torch.clamp(p @ mel_t, min=amin))
             ov[b, :, :n_mels] = 0
+            if L == 0:
+                continue
+            p = sv[b, :L, :nb] ** 2 + sv[b, :L, nb:2 * nb] ** 2
+            db = 10 * torch.log10(torch.clamp(p @ E._v(mel_t, nb * n_mels).view(nb, n_mels), min=amin))
             ov[b, :L, :n_mels] = torch.max(db, db.max() - top_db)
     elif name == "srn_trans_conv0":
         x, x_bs, ld_x, lens, w, bias, out, B, T, Fq, C, dil = a
@@ -42,9 +44,11 @@ def emul_transcriber(name, a):
         ov = _tview(out, B, T, (Fq + 2) * C, T * (Fq + 2) * C).view(B, T, Fq + 2, C)
         for b in range(B):
             L = min(int(lens[b]), T)
-            y = torch.nn.functional.conv2d(xv[b, :L, :Fq][None, None], w.view(C, 1, 3, 3), bias, padding=(dil, 1),
-                                           dilation=(dil, 1))[0]
             ov[b] = 0
+            if L == 0:
+                continue
+            y = torch.nn.functional.conv2d(xv[b, :L, :Fq][None, None], E._v(w, C * 9).view(C, 1, 3, 3), E._v(bias, C),
+                                           padding=(dil, 1), dilation=(dil, 1))[0]
             ov[b, :L, 1:Fq + 1] = torch.relu(y).permute(1, 2, 0)
     elif name == "srn_trans_pool":
         x, lens, out, B, T, Fin, C, Cv, flatten, ld_out = a
