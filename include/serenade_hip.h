@@ -244,6 +244,12 @@ int srn_renorm(const float* x, const float* trg_scale, const float* trg_mean, co
  * x (B, T, C) channels-last, w (k, C), y (B, T). */
 int srn_out_conv_tanh(const float* x, const float* w, const float* bias, float* y, int B, int T, int C, int k,
                       float slope, void* stream);
+/* The same stage over a ragged batch: item b holds L_b = min(lens[b], T) rows (lens: device, B int32, each >= 1).
+ * y[b, t] for t < L_b is bit for bit what srn_out_conv_tanh gives for that item alone (B = 1, T = L_b): rows at or
+ * past L_b count as the zero padding of that call and are not read, whatever they hold.  y[b, t] = 0 for
+ * L_b <= t < T.  Kernel choice as in the dense call (C = 32, k = 7 specialised; generic otherwise). */
+int srn_out_conv_tanh_ragged(const float* x, const float* w, const float* bias, float* y, const int32_t* lens, int B,
+                             int T, int C, int k, float slope, void* stream);
 
 /*
  * One residual unit of HiFiGANResidualBlock with use_additional_convs (residual_block.py:243-258, loop body):
@@ -282,6 +288,19 @@ int srn_hifigan_resunit(const SrnResUnitParams* p, void* stream);
  * slope lies outside [0, 1] or one item reaches 2^31 bytes. */
 enum { SRN_RESUNIT_FORM_F32 = 0, SRN_RESUNIT_FORM_SHARED_F32 = 1, SRN_RESUNIT_FORM_BF16X3 = 2 };
 int srn_hifigan_resunit_route(const SrnResUnitParams* p, int32_t out[3]);
+/* The residual unit over a ragged batch: lengths are data, not shape.  `lens`: device array of n_batch int32, each
+ * >= 1; item b holds L_b = min(lens[b], T) rows and is computed exactly as srn_hifigan_resunit computes a call with
+ * n_batch = 1, T = L_b on that item alone -- in every form (resunit_f32.hip, the shared fp32 form, bf16x3) the dense
+ * results bit for bit, because the tile grid (sized by T), the MFMA order and the epilogue order are the dense call's:
+ *   - rows t >= L_b of x and res2 are never read as data (they may hold anything, NaN included);
+ *   - intermediate rows outside [0, L_b) are zero, as conv2's zero padding of the item alone;
+ *   - output rows t >= L_b are left untouched.
+ * A tile lying wholly past its item's end is computed and stores nothing.  The same params, validation and route as
+ * the dense call (p.T sizes the grid); a NULL `lens` is a validation error, nothing is launched.
+ * srn_hifigan_resunit_ragged_route reports what srn_hifigan_resunit_route reports for the same params (the lengths
+ * are device data and cannot steer the route; the argument may be NULL). */
+int srn_hifigan_resunit_ragged(const SrnResUnitParams* p, const int32_t* lens, void* stream);
+int srn_hifigan_resunit_ragged_route(const SrnResUnitParams* p, const int32_t* lens_or_null, int32_t out[3]);
 
 /* SiFiGAN pitch-dependent dilated-conv operand gather (row a9; un-vendored `sifigan` package, parity unpinned):
  * out (B, T, 3C) = [lrelu(x[t]) | lrelu(x[t - r]) | lrelu(x[t + r])], r = rint(d[b, t] * dilation), zero outside. */

@@ -120,6 +120,8 @@ _SIGS = {
     "srn_conv_gemm_forms": (c_int, [POINTER(c_int32), c_int]),
     "srn_hifigan_resunit": (c_int, [POINTER(SrnResUnitParams), _P]),
     "srn_hifigan_resunit_route": (c_int, [POINTER(SrnResUnitParams), POINTER(c_int32)]),
+    "srn_hifigan_resunit_ragged": (c_int, [POINTER(SrnResUnitParams), _P, _P]),
+    "srn_hifigan_resunit_ragged_route": (c_int, [POINTER(SrnResUnitParams), _P, POINTER(c_int32)]),
     "srn_gn_mish_apply": (c_int, [_P, _P, _P, _P, _P, c_int64, _P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
     "srn_resblock_tail": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int,
                                   c_float, c_float, c_int, _P]),
@@ -136,6 +138,7 @@ _SIGS = {
     "srn_weight_norm_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "srn_renorm": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int, _P]),
     "srn_out_conv_tanh": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
+    "srn_out_conv_tanh_ragged": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
     "srn_pd_gather": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_float, _P]),
     "srn_pad_signal": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "srn_logmel": (c_int, [_P, _P, _P, c_int64, c_int, c_int, c_int, c_float, c_int, _P]),

@@ -14,7 +14,8 @@ PCM) and the transposed F0 contour as dataset `lf0` of `U_S.h5` (`.npz` when the
 item's padded length (decoder.py:71-77), so naive padding into a batch would change the output.  `--batch-styles`
 converts all styles of an utterance in one *exact* ragged batch (`Serenade.inference_ragged`: per-item GroupNorm
 statistics, per-item reflection padding, per-item prompt / source offsets), whose results equal the loop's;
-`--batch-utterances N` extends the batch over N source utterances of different lengths.  With
+`--batch-utterances N` extends the batch over N source utterances of different lengths; `--ragged-vocoder` then
+vocodes the batch's mels in one exact ragged call too (`Vocoder.decode_ragged`) instead of one call per length.  With
 `torchrun --nproc-per-node N` the utterance list is split contiguously over the ranks (one GPU each).
 """
 import argparse
@@ -86,6 +87,10 @@ def build_parser():
     p.add_argument("--batch-utterances", type=int, default=1,
                    help="(MI355X build only) convert this many source utterances, with all their styles, per exact "
                         "ragged batch (implies --batch-styles); outputs equal the one-by-one loop")
+    p.add_argument("--ragged-vocoder", action="store_true",
+                   help="(MI355X build only; with --batch-styles / --batch-utterances) vocode the mels of a batch in "
+                        "ONE ragged HiFi-GAN call (Vocoder.decode_ragged: lengths are data, every item is computed as "
+                        "its own B = 1 call) instead of one call, plan and captured graph per distinct length")
     p.add_argument("--sifigan-checkpoint", type=str, default=None,
                    help="(MI355X build only) also run the recipe's stage 9 in this process: re-analyse every converted "
                         "waveform on the GPU (serenade_amd.world.Analyzer) and write NAME_sifigan.wav from this SiFiGAN "
@@ -210,7 +215,8 @@ class DecodeJob:
     def _run_jobs(self, jobs, batched):
         """convert and write a list of jobs; batched: ONE exact ragged batch for the model (every item = its own B = 1
         call) and one vocoder batch per distinct length (HiFi-GAN has no cross-item arithmetic, but its edge padding
-        sits at the tensor's end, so only equal lengths share a batch)"""
+        sits at the tensor's end, so only equal lengths share a dense batch) -- or, with --ragged-vocoder, one ragged
+        vocoder call for all of them"""
         if not jobs:
             return 0
         out = self.args.outdir
@@ -218,13 +224,16 @@ class DecodeJob:
             mels = self.model.inference_ragged(
                 [(x[0], sc[0], ld[0], r["cvec"][0], r["mel"][0], r["score"][0], r["loud"][0])
                  for _, _, x, sc, ld, r, _ in jobs])
-            waves = [None] * len(jobs)
-            by_len = {}
-            for i, m in enumerate(mels):
-                by_len.setdefault(m.shape[0], []).append(i)
-            for idx in by_len.values():
-                for i, w in zip(idx, self.vocoder.decode_batch(torch.stack([mels[i] for i in idx]))):
-                    waves[i] = w
+            if self.args.ragged_vocoder:
+                waves = self.vocoder.decode_ragged(mels)
+            else:
+                waves = [None] * len(jobs)
+                by_len = {}
+                for i, m in enumerate(mels):
+                    by_len.setdefault(m.shape[0], []).append(i)
+                for idx in by_len.values():
+                    for i, w in zip(idx, self.vocoder.decode_batch(torch.stack([mels[i] for i in idx]))):
+                        waves[i] = w
         else:
             waves = []
             for _, _, x, sc, ld, r, _ in jobs:
@@ -284,6 +293,8 @@ class DecodeJob:
 def main(argv=None):
     args = build_parser().parse_args(argv)
     _setup_logging(args.verbose)
+    if args.ragged_vocoder and not (args.batch_styles or args.batch_utterances > 1):
+        raise SystemExit("--ragged-vocoder needs --batch-styles or --batch-utterances N (N > 1)")
     os.makedirs(args.outdir, exist_ok=True)
     DecodeJob(args).run()
 

@@ -299,6 +299,16 @@ constexpr int SRN_RESUNIT_HALO_MAX = 50;  // the same span as the fused residual
 constexpr int SRN_STRIP_BM = 128;     // conv_strip.hip: output rows per tile (4 waves x 32 rows)
 constexpr int SRN_MAX_KSPLIT = 8;     // conv_splitk.hip: most K slices of one launch
 
+// Kernels with a dense and a ragged instance (lengths as data) take the lengths as a trailing argument pack: empty in
+// the dense instance, whose argument list and code stay what they were, one SrnLens in the ragged one.  The pointer is
+// restrict-qualified so that the compiler may read a length with a scalar load although the kernel also stores (without
+// it the read is a vector load plus a readfirstlane).  srn_first: the pack's one argument.
+using SrnLens = const int32_t* __restrict__;
+template <class A, class... Rest>
+__device__ __forceinline__ A srn_first(const A a, const Rest...) {
+  return a;
+}
+
 // what resunit.hip's resunit_route decides for one validated srn_hifigan_resunit call
 struct SrnResUnitRoute {
   int form;         // SRN_RESUNIT_FORM_*
@@ -308,9 +318,10 @@ struct SrnResUnitRoute {
 };
 // intermediate rows per tile, in every form of the kernel
 constexpr int srn_resunit_bmi(const int C) { return C == 32 ? 256 : 128; }
-// resunit_f32.hip: whether that form takes the (validated) call, and its launch
+// resunit_f32.hip: whether that form takes the (validated) call, and its launch (lens: NULL, or the per-item lengths of
+// srn_hifigan_resunit_ragged)
 bool srn_resunit_f32_eligible(const SrnResUnitParams& p, const SrnResUnitRoute& r);
-int srn_resunit_f32_launch(const SrnResUnitParams& p, const SrnResUnitRoute& r, hipStream_t stream);
+int srn_resunit_f32_launch(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int32_t* lens, hipStream_t stream);
 
 // lowest tap offset and the span (max - min) of the taps
 inline int srn_tap_span(const SrnConvParams& p, int& lo) {

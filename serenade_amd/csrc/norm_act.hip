@@ -337,16 +337,30 @@ __global__ void renorm_kernel(const float* __restrict__ x, const float* __restri
 // is conflict-free) and every lane then forms one output from LDS.  The round-1 kernel read its 7 x 128 B per lane
 // straight from global memory, 64 different lines per load instruction (1.2 TB/s).
 constexpr int OC_BT = 256;
-template <int K, int CC>
+// One kernel text, two instances each.  Dense (RAGGED = false, no `lens` argument: arguments and code as before the
+// ragged entry point existed, L folds to T).  Ragged (RAGGED = true, one trailing argument: the per-item lengths,
+// srn_out_conv_tanh_ragged): item b is the dense B = 1 call at T = L_b = min(lens[b], T) -- the same rows staged, the
+// same fmaf chain -- and y[b, L_b .. T) = 0.  L_b is one uniform scalar load per workgroup; input rows >= L_b are not
+// read, and a tile wholly past the item's end only writes its zeros.
+template <int K, int CC, bool RAGGED = false, class... Lens>
 __global__ __launch_bounds__(256) void out_conv_tanh_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ bias, float* __restrict__ y,
-                                                            int T, float slope) {
+                                                            int T, float slope, const Lens... lens) {
+  static_assert(sizeof...(Lens) == (RAGGED ? 1 : 0), "the ragged instance takes the lengths, the dense one nothing");
   constexpr int PITCH = CC + 4;  // floats
   constexpr int ROWS = OC_BT + K - 1;
   __shared__ __attribute__((aligned(16))) float sx[ROWS * PITCH];
   __shared__ __attribute__((aligned(16))) float sw[K * CC];
   const int b = blockIdx.y;
   const int t0 = blockIdx.x * OC_BT;
+  int L = T;
+  if constexpr (RAGGED) {
+    L = max(min(srn_first(lens...)[b], T), 0);
+    if (t0 >= L) {  // uniform: the whole tile lies past the item's end
+      if (t0 + (int)threadIdx.x < T) y[(int64_t)b * T + t0 + threadIdx.x] = 0.f;
+      return;
+    }
+  }
   const float* xb = x + (int64_t)b * T * CC;
   for (int i = threadIdx.x; i < K * CC; i += 256) sw[i] = w[i];
   constexpr int C4 = CC / 4;
@@ -354,12 +368,18 @@ __global__ __launch_bounds__(256) void out_conv_tanh_kernel(const float* __restr
     const int r = i / C4, c4 = i - r * C4;
     const int ti = t0 + r - (K - 1) / 2;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ti >= 0 && ti < T) v = leaky4(*reinterpret_cast<const float4*>(xb + (int64_t)ti * CC + c4 * 4), slope);
+    if (ti >= 0 && ti < L) v = leaky4(*reinterpret_cast<const float4*>(xb + (int64_t)ti * CC + c4 * 4), slope);
     *reinterpret_cast<float4*>(sx + r * PITCH + c4 * 4) = v;
   }
   __syncthreads();
   const int t = t0 + threadIdx.x;
   if (t >= T) return;
+  if constexpr (RAGGED) {
+    if (t >= L) {
+      y[(int64_t)b * T + t] = 0.f;
+      return;
+    }
+  }
   float acc = bias[0];
 #pragma unroll
   for (int j = 0; j < K; ++j) {
@@ -378,17 +398,27 @@ __global__ __launch_bounds__(256) void out_conv_tanh_kernel(const float* __restr
 }
 
 // generic (any C % 4 == 0, k <= 16) fallback of the above
+template <bool RAGGED = false, class... Lens>
 __global__ __launch_bounds__(256) void out_conv_tanh_generic(const float* __restrict__ x, const float* __restrict__ w,
                                                              const float* __restrict__ bias, float* __restrict__ y,
-                                                             int T, int C, int K, float slope) {
+                                                             int T, int C, int K, float slope, const Lens... lens) {
+  static_assert(sizeof...(Lens) == (RAGGED ? 1 : 0), "the ragged instance takes the lengths, the dense one nothing");
   const int b = blockIdx.y;
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= T) return;
+  int L = T;
+  if constexpr (RAGGED) {
+    L = max(min(srn_first(lens...)[b], T), 0);
+    if (t >= L) {
+      y[(int64_t)b * T + t] = 0.f;
+      return;
+    }
+  }
   const float* xb = x + (int64_t)b * T * C;
   float acc = bias[0];
   for (int j = 0; j < K; ++j) {
     const int ti = t + j - (K - 1) / 2;
-    if (ti < 0 || ti >= T) continue;
+    if (ti < 0 || ti >= L) continue;
     for (int c = 0; c < C; ++c) {
       float v = xb[(int64_t)ti * C + c];
       v = v > 0.f ? v : v * slope;
@@ -567,7 +597,23 @@ extern "C" int srn_out_conv_tanh(const float* x, const float* w, const float* bi
   if (C == 32 && k == 7 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
     hipLaunchKernelGGL((out_conv_tanh_kernel<7, 32>), grid, dim3(256), 0, (hipStream_t)stream, x, w, bias, y, T, slope);
   } else {
-    hipLaunchKernelGGL(out_conv_tanh_generic, grid, dim3(256), 0, (hipStream_t)stream, x, w, bias, y, T, C, k, slope);
+    hipLaunchKernelGGL((out_conv_tanh_generic<>), grid, dim3(256), 0, (hipStream_t)stream, x, w, bias, y, T, C, k, slope);
+  }
+  SRN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int srn_out_conv_tanh_ragged(const float* x, const float* w, const float* bias, float* y,
+                                        const int32_t* lens, int B, int T, int C, int k, float slope, void* stream) {
+  SRN_CHECK_ARG(x && w && bias && y && lens && B > 0 && T > 0 && C > 0 && k > 0 && k % 2 == 1 && k <= 16,
+                "out_conv_tanh_ragged: bad args");
+  dim3 grid((T + 255) / 256, B);
+  if (C == 32 && k == 7 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {  // the dense entry point's choice
+    hipLaunchKernelGGL((out_conv_tanh_kernel<7, 32, true, SrnLens>), grid, dim3(256), 0, (hipStream_t)stream, x,
+                       w, bias, y, T, slope, lens);
+  } else {
+    hipLaunchKernelGGL((out_conv_tanh_generic<true, SrnLens>), grid, dim3(256), 0, (hipStream_t)stream, x, w,
+                       bias, y, T, C, k, slope, lens);
   }
   SRN_CHECK_LAUNCH();
   return 0;

@@ -50,9 +50,18 @@ struct RCfg {
   static_assert(G * C * 8 % NTH == 0, "stage pieces must divide over the workgroup");
 };
 
-template <class R>
+// One kernel text, two instances.  Dense (RAGGED = false, no `lens` argument: the kernel's arguments and code are what
+// they were before the ragged entry point existed -- item_len() folds to T).  Ragged (RAGGED = true, one trailing
+// argument: the per-item lengths, srn_hifigan_resunit_ragged): item z is computed as the dense call with n_batch = 1,
+// T = L_z = min(lens[z], T) computes it; L_z takes T's place where the receptive field is loaded (validity and the
+// clamped address: rows >= L_z are never read), in the intermediate mask and in row_end, while T still sizes the tile
+// grid.  L_z is one wave-uniform scalar load per tile (and one for the prefetched tile).  A tile wholly past its item's
+// end is computed and stores nothing: the weight pipeline (wj / wbuf, two stages in flight across tiles) advances as
+// on any other tile.
+template <class R, bool RAGGED = false, class... Lens>
 __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnResUnitParams p, const int tiles_per_z,
-                                                            const int n_tiles) {
+                                                            const int n_tiles, const Lens... lens) {
+  static_assert(sizeof...(Lens) == (RAGGED ? 1 : 0), "the ragged instance takes the lengths, the dense one nothing");
   constexpr int C = R::C, CH = R::CH, NT = R::NTW, MT = R::MTW, BMI = R::BMI, G = R::G, NTH = R::NTH;
   constexpr bool BF = R::PREC != 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_r[];
@@ -71,6 +80,11 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
   const int U = k * CH;                  // weight units per conv
   const int S = (U + G - 1) / G;         // weight stages per conv
   const float slope = p.slope;
+  // rows of item z that exist: T, or the item's own length (clamped to [0, T]: a bad length cannot reach past the item)
+  auto item_len = [&](const int z) {
+    if constexpr (RAGGED) return max(min(__builtin_amdgcn_readfirstlane(srn_first(lens...)[z]), T), 0);
+    else return T;
+  };
 
   // ---- weight stages: j in [0, 2 S): conv1's stages then conv2's.  Piece q = tid + 256 i of a stage is 16-B
   //      piece (tid & 7) of weight row n = (tid >> 3) + 32 (i & 1) [C = 64] of unit i >> 1 [C = 64] / i [C = 32]:
@@ -126,13 +140,14 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
     const int t0 = (tile - z * tiles_per_z) * BMo;
     const float* xz = p.x + (int64_t)z * p.x_bs + a_f4 * 4;
     const int ti0 = t0 - p2 - p1 + a_r0;
+    const int Tz = item_len(z);
     pa_ok = 0;
 #pragma unroll
     for (int j = 0; j < A_LD; ++j) {
       const int ti = ti0 + RSTEP * j;
-      const bool ok = a_r0 + RSTEP * j < hr && ti >= 0 && ti < T;
+      const bool ok = a_r0 + RSTEP * j < hr && ti >= 0 && ti < Tz;
       pa_ok |= (ok ? 1u : 0u) << j;
-      pa[j] = *reinterpret_cast<const float4*>(xz + min(max(ti, 0), T - 1) * C);
+      pa[j] = *reinterpret_cast<const float4*>(xz + (RAGGED ? max(min(ti, Tz - 1), 0) : min(max(ti, 0), T - 1)) * C);
     }
   };
   // LDS offset of piece j = a_dst0 + j * RSTEP rows (RSTEP is a multiple of 4: the swizzle key does not change)
@@ -276,6 +291,7 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
   for (; tile < n_tiles; tile += gridDim.x) {
     const int z = tile / tiles_per_z;
     const int t0 = (tile - z * tiles_per_z) * BMo;
+    const int Tz = item_len(z);
     stage_a();  // the previous tile's conv2 ended on a barrier: nobody reads the image any more
     __syncthreads();
     const int next = tile + gridDim.x;
@@ -304,7 +320,7 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
             const int gi = t0 - p2 + mrow0 + i;
             float v = acc[m][n][4 * gq + i] + bias;
             v = v > 0.f ? v : v * slope;
-            if (gi < 0 || gi >= T) v = 0.f;
+            if (gi < 0 || gi >= Tz) v = 0.f;
             if constexpr (BF) {
               const __bf16 h = (__bf16)v;
               const __bf16 l = (__bf16)(v - (float)h);
@@ -329,7 +345,7 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
     const float* qz = p.res2 ? p.res2 + (int64_t)z * p.res2_bs + (int64_t)t0 * C : nullptr;  // may alias out
     float* oz = p.out + (int64_t)z * p.out_bs + (int64_t)t0 * C;
     const bool divide = p.post_div != 0.f && p.post_div != 1.f;
-    const int row_end = min(BMo, T - t0);
+    const int row_end = min(BMo, Tz - t0);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int m = 0; m < MT; ++m)
@@ -362,12 +378,22 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
   }
 }
 
+// lens: NULL for the dense call, or the ragged call's per-item lengths (device, n_batch int32)
 template <class R>
-int launch_resunit(const SrnResUnitParams& p, const SrnResUnitRoute& r, hipStream_t stream) {
-  static SrnSmemAttr smem_attr;
-  if (const int e = smem_attr.ensure(reinterpret_cast<const void*>(&resunit_kernel<R>), R::SMEM)) return e;
+int launch_resunit(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int32_t* lens, hipStream_t stream) {
   static_assert(R::BMI == srn_resunit_bmi(R::C), "the route's tile height is the kernel's");
-  hipLaunchKernelGGL((resunit_kernel<R>), dim3(r.grid), dim3(R::NTH), R::SMEM, stream, p, r.tiles_per_z, r.n_tiles);
+  if (lens) {
+    static SrnSmemAttr smem_attr_ragged;
+    if (const int e = smem_attr_ragged.ensure(reinterpret_cast<const void*>(&resunit_kernel<R, true, SrnLens>),
+                                              R::SMEM))
+      return e;
+    hipLaunchKernelGGL((resunit_kernel<R, true, SrnLens>), dim3(r.grid), dim3(R::NTH), R::SMEM, stream, p, r.tiles_per_z,
+                       r.n_tiles, lens);
+  } else {
+    static SrnSmemAttr smem_attr;
+    if (const int e = smem_attr.ensure(reinterpret_cast<const void*>(&resunit_kernel<R>), R::SMEM)) return e;
+    hipLaunchKernelGGL((resunit_kernel<R>), dim3(r.grid), dim3(R::NTH), R::SMEM, stream, p, r.tiles_per_z, r.n_tiles);
+  }
   SRN_CHECK_LAUNCH();
   return 0;
 }
@@ -420,19 +446,41 @@ extern "C" int srn_hifigan_resunit_route(const SrnResUnitParams* pp, int32_t out
   return 0;
 }
 
-extern "C" int srn_hifigan_resunit(const SrnResUnitParams* pp, void* stream_) {
-  SrnResUnitRoute r;
-  if (const int e = resunit_route(pp, r)) return e;
-  const SrnResUnitParams& p = *pp;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+namespace {
+
+// the launch of a routed call: `lens` NULL (srn_hifigan_resunit) or the per-item lengths (srn_hifigan_resunit_ragged)
+int resunit_launch(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int32_t* lens, hipStream_t stream) {
   switch (r.form) {
     case SRN_RESUNIT_FORM_BF16X3:
-      return p.C == 32 ? launch_resunit<RCfg<32, 1>>(p, r, stream) : launch_resunit<RCfg<64, 1>>(p, r, stream);
+      return p.C == 32 ? launch_resunit<RCfg<32, 1>>(p, r, lens, stream) : launch_resunit<RCfg<64, 1>>(p, r, lens, stream);
     case SRN_RESUNIT_FORM_F32:
-      return srn_resunit_f32_launch(p, r, stream);
+      return srn_resunit_f32_launch(p, r, lens, stream);
     default:
       // eight waves per workgroup (A/B on the B = 8 x T = 1024 vocoder, 4 -> 8 waves: k 3 units 0.62 -> 0.51 ms,
       // k 7 1.17 -> 1.05, k 11 1.74 -> 1.61 at C = 64; all 18 units 16.7 -> 14.9 ms)
-      return p.C == 32 ? launch_resunit<RCfg<32, 0, 8>>(p, r, stream) : launch_resunit<RCfg<64, 0, 8>>(p, r, stream);
+      return p.C == 32 ? launch_resunit<RCfg<32, 0, 8>>(p, r, lens, stream)
+                       : launch_resunit<RCfg<64, 0, 8>>(p, r, lens, stream);
   }
+}
+
+}  // namespace
+
+extern "C" int srn_hifigan_resunit(const SrnResUnitParams* pp, void* stream_) {
+  SrnResUnitRoute r;
+  if (const int e = resunit_route(pp, r)) return e;
+  return resunit_launch(*pp, r, nullptr, reinterpret_cast<hipStream_t>(stream_));
+}
+
+// The ragged call: the dense call's validation and route (resunit_route, stated once: T sizes the tile grid whatever
+// the lengths hold), then the same form's RAGGED instantiation.
+extern "C" int srn_hifigan_resunit_ragged_route(const SrnResUnitParams* pp, const int32_t* lens_or_null, int32_t out[3]) {
+  (void)lens_or_null;  // device data: the route cannot depend on it
+  return srn_hifigan_resunit_route(pp, out);
+}
+
+extern "C" int srn_hifigan_resunit_ragged(const SrnResUnitParams* pp, const int32_t* lens, void* stream_) {
+  SrnResUnitRoute r;
+  if (const int e = resunit_route(pp, r)) return e;
+  SRN_CHECK_ARG(lens != nullptr, "resunit_ragged: null lens");
+  return resunit_launch(*pp, r, lens, reinterpret_cast<hipStream_t>(stream_));
 }

@@ -41,9 +41,17 @@ struct UCfg {
   static_assert(G * C * 8 == NTH, "one 16-B weight piece per thread per stage");
 };
 
-template <class R>
+// One kernel text, two instances.  Dense (RAGGED = false, no `lens` argument: the kernel's arguments and code are what
+// they were before the ragged entry point existed -- item_len() folds to T).  Ragged (RAGGED = true, one trailing
+// argument: the per-item lengths): item z is computed as the dense call with n_batch = 1, T = L_z = min(lens[z], T)
+// computes it -- L_z takes T's place in the receptive field's descriptor, the intermediate mask and row_end, while T
+// still sizes the tile grid.  L_z is one wave-uniform scalar load per tile (and one for the prefetched tile); nothing
+// per element.  A tile that lies wholly past its item's end is computed and stores nothing (row_end <= 0): the weight
+// pipeline (wj / wbuf, two stages in flight across tiles) advances exactly as on any other tile.
+template <class R, bool RAGGED = false, class... Lens>
 __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitParams p, const int tiles_per_z,
-                                                             const int n_tiles, const FDiv d_tpz) {
+                                                             const int n_tiles, const FDiv d_tpz, const Lens... lens) {
+  static_assert(sizeof...(Lens) == (RAGGED ? 1 : 0), "the ragged instance takes the lengths, the dense one nothing");
   constexpr int C = R::C, CH = R::CH, BMI = R::BMI, G = R::G;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_u[];
   unsigned char* const sA = smem_u;
@@ -61,6 +69,11 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
   const int U = k * CH;                // weight units per conv
   const int S = (U + G - 1) / G;       // weight stages per conv
   const float slope = p.slope;
+  // rows of item z that exist: T, or the item's own length (clamped to [0, T]: a bad length cannot reach past the item)
+  auto item_len = [&](const int z) {
+    if constexpr (RAGGED) return max(min(__builtin_amdgcn_readfirstlane(srn_first(lens...)[z]), T), 0);
+    else return T;
+  };
 
   // ---- weight stages j in [0, 2 S): conv1's then conv2's.  This thread's piece: 16-B piece (tid & 7) of weight row n
   //      of unit u0 + g of the stage -- row and piece in the per-lane offset, the unit in the scalar offset
@@ -90,7 +103,7 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
   auto load_a = [&](const int tile) {
     const int z = fdiv(tile, d_tpz);
     const int t0 = (tile - z * tiles_per_z) * BMo;
-    const __amdgpu_buffer_rsrc_t rs_x = srn_buffer_rsrc(p.x + (int64_t)z * p.x_bs, T * C * 4);
+    const __amdgpu_buffer_rsrc_t rs_x = srn_buffer_rsrc(p.x + (int64_t)z * p.x_bs, item_len(z) * C * 4);
     const int v0 = a_voff + (t0 - p2 - p1) * (C * 4);  // negative rows wrap to offsets >= 2^31: out of range, zeros
 #pragma unroll
     for (int j = 0; j < A_LD; ++j) pa[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, v0 + j * (RSTEP * C * 4), 0, 0);
@@ -174,6 +187,7 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
   for (; tile < n_tiles; tile += gridDim.x) {
     const int z = fdiv(tile, d_tpz);
     const int t0 = (tile - z * tiles_per_z) * BMo;
+    const int Tz = item_len(z);
     stage_a();  // the previous tile's conv2 ended on a barrier: nobody reads the image any more
     __syncthreads();
     const int next = tile + gridDim.x;
@@ -184,7 +198,7 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
     conv_pass(dil);
     // ---- intermediate = LeakyReLU(conv1 + b1), zero outside [0, T), over the image (every wave passed the last
     //      stage's barrier, so no conv1 read is pending)
-    if (t0 - p2 >= 0 && t0 - p2 + BMI <= T) {
+    if (t0 - p2 >= 0 && t0 - p2 + BMI <= Tz) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float v = acc[r] + bias1;
@@ -197,7 +211,7 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
         const int gi = t0 - p2 + wm0 + 4 * lh + dr;
         float v = acc[r] + bias1;
         v = fmaxf(v, v * slope);
-        if (gi < 0 || gi >= T) v = 0.f;
+        if (gi < 0 || gi >= Tz) v = 0.f;
         *reinterpret_cast<float*>(sA + mid_lane + dr * 144) = v;
       }
     }
@@ -209,7 +223,7 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
 
     // ---- epilogue: + b2 + x [+ res2] [/ post_div]; rows [t0, t0 + BMo) and < T.  out never aliases x; res2 may be
     //      out itself (running stage sum): every element is loaded by the lane that later stores it
-    const int row_end = min(BMo, T - t0);
+    const int row_end = RAGGED ? max(min(BMo, Tz - t0), 0) : min(BMo, T - t0);
     const int64_t zoff = (int64_t)t0 * C;
     const int io_bytes = row_end * C * 4;  // the tile's rows that exist: anything past them is out of range
     const __amdgpu_buffer_rsrc_t rs_xe = srn_buffer_rsrc(p.x + (int64_t)z * p.x_bs + zoff, io_bytes);
@@ -255,12 +269,21 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
 }
 
 template <class R>
-int launch_unit(const SrnResUnitParams& p, const SrnResUnitRoute& r, hipStream_t stream) {
-  static SrnSmemAttr smem_attr;
-  if (const int e = smem_attr.ensure(reinterpret_cast<const void*>(&resunit_f32_kernel<R>), R::SMEM)) return e;
+int launch_unit(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int32_t* lens, hipStream_t stream) {
   static_assert(R::BMI == srn_resunit_bmi(R::C), "the route's tile height is the kernel's");
-  hipLaunchKernelGGL((resunit_f32_kernel<R>), dim3(r.grid), dim3(NTH), R::SMEM, stream, p, r.tiles_per_z, r.n_tiles,
-                     make_fdiv((uint32_t)r.tiles_per_z));
+  if (lens) {
+    static SrnSmemAttr smem_attr_ragged;
+    if (const int e = smem_attr_ragged.ensure(reinterpret_cast<const void*>(&resunit_f32_kernel<R, true, SrnLens>),
+                                              R::SMEM))
+      return e;
+    hipLaunchKernelGGL((resunit_f32_kernel<R, true, SrnLens>), dim3(r.grid), dim3(NTH), R::SMEM, stream, p, r.tiles_per_z,
+                       r.n_tiles, make_fdiv((uint32_t)r.tiles_per_z), lens);
+  } else {
+    static SrnSmemAttr smem_attr;
+    if (const int e = smem_attr.ensure(reinterpret_cast<const void*>(&resunit_f32_kernel<R>), R::SMEM)) return e;
+    hipLaunchKernelGGL((resunit_f32_kernel<R>), dim3(r.grid), dim3(NTH), R::SMEM, stream, p, r.tiles_per_z, r.n_tiles,
+                       make_fdiv((uint32_t)r.tiles_per_z));
+  }
   SRN_CHECK_LAUNCH();
   return 0;
 }
@@ -275,6 +298,7 @@ bool srn_resunit_f32_eligible(const SrnResUnitParams& p, const SrnResUnitRoute& 
   return r.n_tiles < (1 << 26);                                    // fdiv's range
 }
 
-int srn_resunit_f32_launch(const SrnResUnitParams& p, const SrnResUnitRoute& r, hipStream_t stream) {
-  return p.C == 32 ? launch_unit<UCfg<32>>(p, r, stream) : launch_unit<UCfg<64>>(p, r, stream);
+// lens: NULL for the dense call, or the ragged call's per-item lengths (device, n_batch int32)
+int srn_resunit_f32_launch(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int32_t* lens, hipStream_t stream) {
+  return p.C == 32 ? launch_unit<UCfg<32>>(p, r, lens, stream) : launch_unit<UCfg<64>>(p, r, lens, stream);
 }

@@ -174,6 +174,26 @@ class ResUnitOp(_StructOp):
         return p
 
 
+class RaggedResUnitOp(_StructOp):
+    """A prebuilt srn_hifigan_resunit_ragged call: ResUnitOp's keywords plus `lens`, the (n_batch,) int32 device tensor
+    of per-item row counts, read when the op RUNS (a plan rewrites it in place between runs).  Item b is computed as
+    its own n_batch = 1, T = lens[b] dense call; rows at or past lens[b] are neither read nor written."""
+
+    __slots__ = ("_wplanes", "_lens")
+    _profiled = True
+
+    def __init__(self, **kw):
+        super().__init__("srn_hifigan_resunit_ragged", kw)
+        entry, lens = self._fn, ctypes.c_void_p(_ptr(self._lens))
+        self._fn = lambda p, stream: entry(p, lens, stream)
+
+    def _fill(self, *, lens, **kw):
+        if not (isinstance(lens, torch.Tensor) and lens.dtype == torch.int32 and lens.numel() >= int(kw["n_batch"])):
+            raise TypeError("RaggedResUnitOp: lens must be an int32 tensor of n_batch entries")
+        self._lens = lens
+        return ResUnitOp._fill(self, **kw)  # the dense op's struct, weight planes included
+
+
 class MultiCopyOp:
     """srn_multi_copy: many small device-to-device copies as one launch per 160 entries -- src tensor i (contiguous
     fp32) goes to dst.view(-1)[offs[i] : offs[i] + src.numel()].  The table travels in the kernel arguments, so the call
@@ -453,6 +473,13 @@ def renorm_op(x, trg_scale, trg_mean, voc_mean, voc_scale, y, rows, C):
 
 def out_conv_tanh_op(x, w, bias, y, B, T, C, k, slope):
     return CallOp("srn_out_conv_tanh", (x, w, bias, y, B, T, C, k, slope))
+
+
+def out_conv_tanh_ragged_op(x, w, bias, y, lens, B, T, C, k, slope):
+    """out_conv_tanh_op over a ragged batch: lens (B,) int32 rows per item; y is zero past each item's end"""
+    if lens.dtype != torch.int32:
+        raise TypeError("out_conv_tanh_ragged_op: lens must be int32")
+    return CallOp("srn_out_conv_tanh_ragged", (x, w, bias, y, lens, B, T, C, k, slope))
 
 
 def pd_gather_op(x, d, out, B, T, C, dilation, slope):

@@ -22,7 +22,7 @@ import yaml
 from . import _shapes, ops
 from .models import _Packed, _fold_wn
 from .ops import ACT_LEAKY, POST_DIV, POST_LEAKY, RES_ADD
-from .plan import conv_op, dev_f32, lru_get, require_cuda as _require_cuda
+from .plan import conv_op, dev_f32, item_lengths, lru_get, require_cuda as _require_cuda, rup
 
 __all__ = ["HiFiGANGenerator", "Vocoder", "load_vocoder", "hifigan_state_shapes"]
 
@@ -126,6 +126,13 @@ class HiFiGANGenerator(_Packed):
         key = (B, T, ops.DEFAULT_PRECISION)
         return lru_get(self._plans, key, 4, lambda: HiFiGANPlan(self, B, T))
 
+    def plan_ragged(self, B, T_max, bucket=None):
+        """the ragged plan for B items of at most T_max frames: its capacity is T_max rounded up to `bucket` frames
+        (RAGGED_BUCKET), so one plan serves every batch of B whose longest item falls in the same bucket"""
+        T_cap = rup(T_max, RAGGED_BUCKET if bucket is None else int(bucket))
+        key = ("ragged", B, T_cap, ops.DEFAULT_PRECISION)
+        return lru_get(self._plans, key, 4, lambda: RaggedHiFiGANPlan(self, B, T_cap))
+
     @torch.no_grad()
     def forward(self, c):
         """(B, in_channels, T) -> (B, 1, T * hop)   (hifigan.py:171-190)."""
@@ -151,14 +158,52 @@ class HiFiGANGenerator(_Packed):
         return y.squeeze(0).transpose(1, 0)
 
     @torch.no_grad()
-    def inference_batch(self, c, normalize_before=False):
-        """(B, T, in_channels) -> (B, 1, T * hop)   (hifigan.py:267-284)."""
+    def inference_batch(self, c, normalize_before=False, lengths=None):
+        """(B, T, in_channels) -> (B, 1, T * hop)   (hifigan.py:267-284).  lengths (B frame counts in [1, T]): the
+        batch is ragged -- item b is vocoded as its own B = 1 call on its first lengths[b] frames (the rows behind
+        them may hold anything) and the output is zero past lengths[b] * hop."""
         if not isinstance(c, torch.Tensor):
             c = torch.tensor(c, dtype=torch.float).to(self._device())
         _require_cuda(c, "HiFiGANGenerator.inference_batch")
+        if lengths is not None:
+            lengths = item_lengths(lengths, c.shape[0], c.shape[1], "HiFiGANGenerator.inference_batch")
         if normalize_before:
             c = (c - self.mean) / self.scale
-        return self._run_cl(c.detach().to(torch.float32).contiguous())
+        c = c.detach().to(torch.float32).contiguous()
+        if lengths is None:
+            return self._run_cl(c)
+        pl = self._run_ragged(c.shape[0], c.shape[1], lengths, lambda pl: pl.c_in[:, :c.shape[1]].copy_(c))
+        return pl.wave[:, :c.shape[1] * self.hop].clone().unsqueeze(1)
+
+    @torch.no_grad()
+    def inference_ragged(self, cs, normalize_before=False):
+        """[(T_b, in_channels)] -> [(T_b * hop,)]: utterances of different lengths in ONE call, each computed as its
+        own B = 1 inference."""
+        cs = [c if isinstance(c, torch.Tensor) else torch.tensor(c, dtype=torch.float).to(self._device()) for c in cs]
+        if not cs:
+            raise ValueError("HiFiGANGenerator.inference_ragged: no items")
+        for c in cs:
+            _require_cuda(c, "HiFiGANGenerator.inference_ragged")
+        if normalize_before:
+            cs = [(c - self.mean) / self.scale for c in cs]
+        lengths = item_lengths([c.shape[0] for c in cs], len(cs), max(c.shape[0] for c in cs),
+                               "HiFiGANGenerator.inference_ragged")
+
+        def fill(pl):
+            for b, c in enumerate(cs):
+                pl.c_in[b, :c.shape[0]].copy_(c.detach())
+        pl = self._run_ragged(len(cs), max(lengths), lengths, fill)
+        return [pl.wave[b, :n * self.hop].clone() for b, n in enumerate(lengths)]
+
+    def _run_ragged(self, B, T_max, lengths, fill):
+        """run the ragged plan of (B, T_max): `fill(plan)` writes the items into plan.c_in (rows past an item's end keep
+        whatever an earlier batch left there: they are never read as data); returns the plan, whose wave holds the
+        result until its next run"""
+        pl = self.plan_ragged(B, T_max)
+        pl.set_lengths(lengths)
+        fill(pl)
+        pl.run()
+        return pl
 
 
 FUSED_UNIT_CHANNELS = (32, 64)  # stage widths whose residual units run as one fused launch (srn_hifigan_resunit)
@@ -169,6 +214,13 @@ class HiFiGANPlan:
     output: self.wave (B, T * hop)."""
 
     def __init__(self, gen, B, T):
+        self._build(gen, B, T, None)
+
+    def _build(self, gen, B, T, lens):
+        """the stage walk of the dense plan and of RaggedHiFiGANPlan.  lens: None, or one (B,) int32 device tensor per
+        stage -- lens[0] for the mel frames, lens[i + 1] behind upsample i -- which makes every length data: each conv
+        gets its input stage's lengths as len_in (rows at or past them read as the zeros an item alone would be padded
+        with), the fused units and the output stage run their ragged entry points."""
         P = gen.packed()
         dev = gen._device()
         self.B, self.T = B, T
@@ -189,15 +241,18 @@ class HiFiGANPlan:
         slope = gen.slope
         ol = []
 
+        masked = (lambda st: {}) if lens is None else (lambda st: {"len_in": lens[st]})
         conv = functools.partial(conv_op, B)
-        ol.append(conv(self.c_in, gen.in_channels, T, P["in_w"], P["in_b"], h, C0, T, ops.conv_taps(gen.kernel_size)))
+        ol.append(conv(self.c_in, gen.in_channels, T, P["in_w"], P["in_b"], h, C0, T, ops.conv_taps(gen.kernel_size),
+                       **masked(0)))
         cur, ccur, tcur = h, C0, T
         nb = gen.num_blocks
         for i, up in enumerate(P["ups"]):
             s, C, Tn = up["s"], up["cout"], Ts[i]
-            for r, (taps, wp) in enumerate(up["phases"]):
+            for r, (taps, wp) in enumerate(up["phases"]):  # a phase reads the stage below: its lengths
                 ol.append(conv(cur, ccur, tcur, wp, up["b"], u, C, tcur, taps, pro_act=ACT_LEAKY, pro_slope=slope,
-                               out_bs=Tn * C, out_t_stride=s, out_t_off=r))
+                               out_bs=Tn * C, out_t_stride=s, out_t_off=r, **masked(i)))
+            here = masked(i + 1)
             for j in range(nb):
                 convs = P["blocks"][i * nb + j]
                 x = u
@@ -214,30 +269,61 @@ class HiFiGANPlan:
                             fin.update(post=POST_DIV, post_div=float(nb))
                     if "w2" in cv and C in FUSED_UNIT_CHANNELS and (cv["k"] - 1) * cv["d"] <= 50 and cv["k"] % 2 == 1:
                         # thin stage: the whole unit in one launch (resunit.hip); stage sum / mean in its epilogue
-                        ol.append(ops.ResUnitOp(x=x, w1=cv["w1"], b1=cv["b1"], w2=cv["w2"], b2=cv["b2"], out=dst,
-                                                n_batch=B, T=Tn, C=C, k=cv["k"], dilation=cv["d"], slope=slope,
-                                                res2=fin.get("res2"), post_div=fin.get("post_div", 0.0)))
+                        unit = dict(x=x, w1=cv["w1"], b1=cv["b1"], w2=cv["w2"], b2=cv["b2"], out=dst, n_batch=B, T=Tn,
+                                    C=C, k=cv["k"], dilation=cv["d"], slope=slope, res2=fin.get("res2"),
+                                    post_div=fin.get("post_div", 0.0))
+                        ol.append(ops.ResUnitOp(**unit) if lens is None
+                                  else ops.RaggedResUnitOp(lens=lens[i + 1], **unit))
                     elif "w2" in cv:
                         # the second LeakyReLU (residual_block.py:252) has one consumer: it runs once per element in
                         # conv1's epilogue, not once per element per 32-deep step per column tile in conv2's loop (on
                         # the fp32 matrix pipe every vector instruction of the loop is taken from the MFMA stream)
                         ol.append(conv(x, C, Tn, cv["w1"], cv["b1"], xt, C, Tn, ops.conv_taps(cv["k"], cv["d"]),
-                                       pro_act=ACT_LEAKY, pro_slope=slope, post=POST_LEAKY, post_div=slope))
+                                       pro_act=ACT_LEAKY, pro_slope=slope, post=POST_LEAKY, post_div=slope, **here))
                         ol.append(conv(xt, C, Tn, cv["w2"], cv["b2"], dst, C, Tn, ops.conv_taps(cv["k"], 1),
-                                       res=x, res_mode=RES_ADD, res_bs=Tn * C, ld_res=C, **fin))
+                                       res=x, res_mode=RES_ADD, res_bs=Tn * C, ld_res=C, **fin, **here))
                     else:
                         ol.append(conv(x, C, Tn, cv["w1"], cv["b1"], dst, C, Tn, ops.conv_taps(cv["k"], cv["d"]),
                                        pro_act=ACT_LEAKY, pro_slope=slope, res=x, res_mode=RES_ADD, res_bs=Tn * C,
-                                       ld_res=C, **fin))
+                                       ld_res=C, **fin, **here))
                     x = dst
             cur, ccur, tcur = acc, C, Tn
             # the next stage's upsample reads `acc` and writes `u`; resblocks then overwrite acc only at their end
-        ol.append(ops.out_conv_tanh_op(cur, P["out_w"], P["out_b"], self.wave, B, tcur, ccur, gen.kernel_size, 0.01))
+        if lens is None:
+            ol.append(ops.out_conv_tanh_op(cur, P["out_w"], P["out_b"], self.wave, B, tcur, ccur, gen.kernel_size, 0.01))
+        else:
+            ol.append(ops.out_conv_tanh_ragged_op(cur, P["out_w"], P["out_b"], self.wave, lens[-1], B, tcur, ccur,
+                                                  gen.kernel_size, 0.01))
         self.ops = ol
         self._runner = ops.GraphRunner(lambda: self.ops)
 
     def run(self):
         self._runner()
+
+
+RAGGED_BUCKET = 64  # frames: a ragged plan's capacity is the batch maximum rounded up to this
+
+
+class RaggedHiFiGANPlan(HiFiGANPlan):
+    """HiFiGANPlan with the lengths as data: one plan (and one captured graph) for every batch of B items whose longest
+    has at most T_cap frames.  Input: self.c_in (B, T_cap, in_ch), rows at or past an item's length may hold anything;
+    output: self.wave (B, T_cap * hop), zero past each item's end.  Item b is computed as its own B = 1 dense plan of
+    lengths[b] frames computes it.  self.lens (n_stages + 1, B) int32 holds the per-stage lengths the ops read when they
+    run: set_lengths() rewrites it in place -- outside the captured graph, whose nodes only carry its address."""
+
+    def __init__(self, gen, B, T_cap):
+        dev = gen._device()
+        self.scales = [1]
+        for s in gen.upsample_scales:
+            self.scales.append(self.scales[-1] * s)
+        self.lens = torch.zeros(len(self.scales), B, dtype=torch.int32, device=dev)
+        self.c_raw = None  # Vocoder: the padded batch in front of the renormalisation
+        self._build(gen, B, T_cap, list(self.lens.unbind(0)))
+
+    def set_lengths(self, lengths):
+        """lengths: B frame counts in [1, T_cap] (validated by the caller, plan.item_lengths)"""
+        host = torch.tensor([[int(n) * s for n in lengths] for s in self.scales], dtype=torch.int32)
+        self.lens.copy_(host)
 
 
 def load_vocoder(checkpoint, config=None, stats=None):
@@ -314,6 +400,45 @@ class Vocoder(object):
         return y, self.config["sampling_rate"]
 
     @torch.no_grad()
-    def decode_batch(self, c):
-        """(B, T, 80) -> (B, T * hop)   (vocoder.py:64-75)."""
-        return self._decode_cl(c)
+    def decode_batch(self, c, lengths=None):
+        """(B, T, 80) -> (B, T * hop)   (vocoder.py:64-75).  lengths (B frame counts in [1, T]): a ragged batch, as
+        HiFiGANGenerator.inference_batch takes it -- zeros past each item's end."""
+        if lengths is None:
+            return self._decode_cl(c)
+        _require_cuda(c, "Vocoder.decode_batch")
+        B, T, _ = c.shape
+        lengths = item_lengths(lengths, B, T, "Vocoder.decode_batch")
+        pl = self._decode_ragged(B, T, lengths, lambda raw: raw[:, :T].copy_(c.detach()))
+        return pl.wave[:, :T * self.model.hop].clone()
+
+    @torch.no_grad()
+    def decode_ragged(self, mels):
+        """[(T_b, 80) normalised mels] -> [(T_b * hop,) waveforms]: one vocoder call for utterances of different
+        lengths, each computed as its own decode()."""
+        mels = list(mels)
+        if not mels:
+            raise ValueError("Vocoder.decode_ragged: no items")
+        for m in mels:
+            _require_cuda(m, "Vocoder.decode_ragged")
+        lengths = item_lengths([m.shape[0] for m in mels], len(mels), max(m.shape[0] for m in mels),
+                               "Vocoder.decode_ragged")
+
+        def fill(raw):
+            for b, m in enumerate(mels):
+                raw[b, :m.shape[0]].copy_(m.detach())
+        pl = self._decode_ragged(len(mels), max(lengths), lengths, fill)
+        return [pl.wave[b, :n * self.model.hop].clone() for b, n in enumerate(lengths)]
+
+    def _decode_ragged(self, B, T_max, lengths, fill):
+        """the padded batch goes through ONE srn_renorm (all T_cap rows of every item: the rows past an item's end are
+        renormalised leftovers, never read as data), then through the ragged plan"""
+        pl = self.model.plan_ragged(B, T_max)
+        if pl.c_raw is None:
+            pl.c_raw = torch.zeros_like(pl.c_in)
+        pl.set_lengths(lengths)
+        fill(pl.c_raw)
+        ts = self.trg_stats if self.take_norm_feat else {"scale": None, "mean": None}
+        ops.renorm_op(pl.c_raw, ts["scale"], ts["mean"], self.stats["mean"], self.stats["scale"], pl.c_in,
+                      pl.c_raw.shape[0] * pl.c_raw.shape[1], pl.c_raw.shape[2])()
+        pl.run()
+        return pl

@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""Developer tool (GPU): HiFi-GAN vocoder throughput, dense against ragged.  The generator is
+the path's HiFi-GAN (serenade_amd.utils.synth.HIFIGAN_PARAMS, procedural weights), driven through `Vocoder` as the
+decode CLI drives it.  Prints one JSON object.
+
+    vocbench.py B T                 the dense `decode_batch` on B utterances of T frames
+    vocbench.py B T --ragged        the same dense call; the ragged call (`decode_batch(lengths=)`) on the same equal
+                                    lengths; then B DISTINCT lengths per batch, a new set every batch as a corpus has
+                                    them, the batch maxima spread over the 128 frames below T: (a) the decode CLI's
+                                    `by_len` loop (one dense call per distinct length: plan build, buffers and -- with
+                                    graphs on -- capture included), (b) one `decode_ragged` call per batch, at bucket
+                                    sizes 1, 32, 64 and 128 frames (plans reused where a batch falls into a bucket seen
+                                    before, dead frames up to the bucket's end computed)
+    --graphs                        replay plans as captured hipGraphs (ops.set_graphs)
+    --passes N                      batches of fresh lengths per measurement (default 6)
+
+Every figure is wall time per batch over the passes, after a warm-up on lengths the passes do not reuse (kernels loaded,
+allocator warm); a median of one run is not a distribution -- repeat the run before relying on a difference of a few
+per cent."""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from serenade_amd import _shapes, build, ops, vocoder  # noqa: E402
+from serenade_amd.utils.synth import HIFIGAN_PARAMS, fill_state_dict  # noqa: E402
+
+BUCKETS = (1, 32, 64, 128)
+
+
+def make_vocoder(dev):
+    gen = vocoder.HiFiGANGenerator(**HIFIGAN_PARAMS)
+    gen.load_state_dict(fill_state_dict(_shapes.as_meta(_shapes.hifigan_shapes(**HIFIGAN_PARAMS, weight_norm=True)),
+                                        seed=0))
+    one = np.ones(80, dtype=np.float32)
+    return vocoder.Vocoder.from_generator(gen, {"sampling_rate": 24000}, {"mean": 0 * one, "scale": one}, dev,
+                                          trg_stats={"mean": 0 * one, "scale": one})
+
+
+def _timed(fn, warm, reps):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps
+
+
+def distinct_length_sets(B, T, n_sets):
+    """n_sets batches of B distinct frame counts, no count in two batches: each batch spread evenly over about half
+    of T below its longest item, the longest items spread evenly over the min(128, T / 2) frames below T -- so the batch
+    maxima fall into one bucket of 128 frames, two of 64, four of 32 and n_sets of 1"""
+    step = max(1, (T // 2) // max(B - 1, 1))
+    gap = min(128, T // 2) // n_sets
+    used, sets = set(), []
+    for s in range(n_sets):
+        lens = []
+        for b in range(B):
+            v = T - s * gap - b * step
+            while v in used:
+                v -= 1
+            if v < 1:
+                sys.exit(f"vocbench: {n_sets} sets of {B} distinct lengths do not fit under {T} frames")
+            used.add(v)
+            lens.append(v)
+        sets.append(lens)
+    return sets
+
+
+def by_len_loop(voc, mels):
+    """what ssc_decode._run_jobs does without --ragged-vocoder"""
+    by_len = {}
+    for i, m in enumerate(mels):
+        by_len.setdefault(m.shape[0], []).append(i)
+    return [voc.decode_batch(torch.stack([mels[i] for i in idx])) for idx in by_len.values()]
+
+
+def main():
+    args = [v for v in sys.argv[1:] if not v.startswith("--")]
+    flags = [v for v in sys.argv[1:] if v.startswith("--")]
+    passes = 6
+    if "--passes" in flags:
+        passes = int(args.pop(2))
+    if set(flags) - {"--ragged", "--graphs", "--passes"}:
+        sys.exit(__doc__)
+    B, T = (int(v) for v in (args[:2] + ["8", "1024"][len(args):]))
+    dev = torch.device("cuda:0")
+    ops.set_graphs("--graphs" in flags)
+    voc = make_vocoder(dev)
+    hop = voc.model.hop
+    rng = np.random.default_rng(0)
+    pool = torch.from_numpy(rng.standard_normal((B, T, 80)).astype(np.float32)).to(dev)
+    out = {"build_id": build.built_id(), "graphs": "--graphs" in flags, "passes": passes,
+           "workload": f"B={B} utterances x {T} frames, hop {hop}"}
+
+    def rate(dt, frames):
+        return {"ms_per_batch": dt * 1e3, "frames_per_s": frames / dt}
+
+    with torch.no_grad():
+        out["dense_equal"] = rate(_timed(lambda: voc.decode_batch(pool), 3, 10), B * T)
+        if "--ragged" in flags:
+            full = [T] * B
+            out["ragged_equal"] = rate(_timed(lambda: voc.decode_batch(pool, lengths=full), 3, 10), B * T)
+            sets = distinct_length_sets(B, T, passes + 1)
+            sets = sets[-1:] + sets[:-1]  # the warm-up batch is the shortest, so every plan of the passes is new
+            frames = sum(sum(s) for s in sets[1:]) / passes
+
+            def corpus(fn):
+                voc.model._plans.clear()
+                fn([pool[b, :n] for b, n in enumerate(sets[0])])  # warm-up on lengths no pass reuses
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for s in sets[1:]:
+                    fn([pool[b, :n] for b, n in enumerate(s)])
+                torch.cuda.synchronize()
+                return rate((time.perf_counter() - t0) / passes, frames)
+
+            out["distinct_by_len_loop"] = corpus(lambda mels: by_len_loop(voc, mels))
+            out["distinct_ragged_call"] = {}
+            for bucket in BUCKETS:
+                vocoder.RAGGED_BUCKET = bucket
+                out["distinct_ragged_call"][f"bucket_{bucket}"] = corpus(voc.decode_ragged)
+    print(json.dumps(out, indent=1))
+
+
+if __name__ == "__main__":
+    main()
