@@ -318,7 +318,8 @@ int srn_gru_recur_last(const float* gi, const float* w_hh_t, const float* b_hh, 
 
 /* StyleTokenLayer (style_encoder.py:235-252 + gst/attention.py:110-184,298-300): ref (B, Dq) -> out (B, F), with its
  * input-independent parts formed at weight-packing time: k, v (n_tok, F) = tanh(embs) W_k^T + b_k / W_v^T + b_v;
- * wq_t (Dq, F), wo_t (F, F) = W_q, W_out transposed. */
+ * wq_t (Dq, F), wo_t (F, F) = W_q, W_out transposed.  Limits: n_head <= 256, F % n_head == 0 and
+ * (2 F + n_head n_tok + Dq) floats of LDS <= 64 KiB; anything past them is refused. */
 int srn_style_token_attention_kv(const float* ref, const float* wq_t, const float* bq, const float* k, const float* v,
                                  const float* wo_t, const float* bo, float* out, int B, int Dq, int n_tok, int F,
                                  int n_head, void* stream);
@@ -331,7 +332,7 @@ int srn_style_token_attention_kv(const float* ref, const float* wq_t, const floa
  */
 /* numpy.pad(x, pad, mode) per batch row, zero-filled up to ld: x (B, n) -> out (B, ld).  mode 0 = "reflect" (what
  * logmelfilterbank passes to librosa.stft, preprocess.py:174-181), 1 = "constant" zeros (librosa.stft's default since
- * 0.10, which loudness_extract's call preprocess.py:131 takes). */
+ * 0.10, which loudness_extract's call preprocess.py:131 takes).  B <= 65535. */
 int srn_pad_signal(const float* x, float* out, int B, int n, int pad, int ld, int mode, void* stream);
 /* out (frames, n_mels) = log_b(max(eps, |spec| @ mel^T)); mel_t (n_bins, n_mels) = filterbank transposed;
  * log_mode 10 / 2 / 0 (natural)  (preprocess.py:176-203). */
@@ -339,7 +340,7 @@ int srn_logmel(const float* spec, const float* mel_t, float* out, int64_t frames
                float eps, int log_mode, void* stream);
 /* out (B, frames) = log(mean_f 10^((max(10 log10(max(amin, |spec|^2)), max_db(utterance) - top_db) + a_weight_db[f])
  * / 20) + add_eps)  (preprocess.py:126-137: power_to_db -> perceptual_weighting -> db_to_amplitude -> mean -> log).
- * gmax_ws: B uint32 of scratch. */
+ * gmax_ws: B uint32 of scratch.  B <= 65535. */
 int srn_loudness(const float* spec, const float* a_weight_db, uint32_t* gmax_ws, float* out, int B, int frames,
                  int n_bins, int ld, float amin, float top_db, float add_eps, void* stream);
 /* The same three for a padded batch of unequal utterances, each item treated as its own B = 1 call treats it (the

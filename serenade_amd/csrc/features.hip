@@ -32,6 +32,26 @@ __global__ __launch_bounds__(256) void pad_signal_kernel(const float* __restrict
   }
 }
 
+// log_b(a), b = e | 2 | 10 (log_mode 0 | 2 | 10), for finite a > 0, to about an ulp of the result at any magnitude.
+// logf / log2f / log10f take the hardware log2 of a itself, which errs by an ulp of ITS result: at the floor
+// a = eps = 1e-10 that is an ulp of 33, and ln(eps) came out two float32 spacings off (3.2e-6; the float64 reference
+// rounds to the spacing between).  So the exponent is split off first: a = m 2^e with m in [sqrt(1/2), sqrt(2)),
+// log2 m is at most 0.5 in magnitude, and e log_b(2) is added from a constant in two parts whose high part has 12 bits
+// (e hi is exact) with one rounding.
+__device__ __forceinline__ float log_base(const float a, const int log_mode) {
+  int e;
+  float m = frexpf(a, &e);  // m in [0.5, 1)
+  if (m < 0.70710678f) {
+    m *= 2.f;
+    --e;
+  }
+  const float l2 = log2f(m), ef = (float)e;
+  if (log_mode == 2) return ef + l2;
+  const float hi = log_mode == 10 ? 0.301025390625f : 0.693145751953125f;  // log_b(2) = hi + lo
+  const float lo = log_mode == 10 ? 4.60503898e-06f : 1.42860682e-06f;
+  return fmaf(ef, hi, fmaf(ef, lo, l2 * (hi + lo)));
+}
+
 // one frame by one workgroup of 128: |X| of the nb bins into LDS (mag), then mel bin m = threadIdx (mel_t is
 // (nb, n_mels): lanes read consecutive addresses), o[m] = log(max(eps, dot)).  The arithmetic of logmel_kernel and
 // logmel_ragged_kernel, stated once.
@@ -47,7 +67,7 @@ __device__ __forceinline__ void logmel_row(const float* __restrict__ row, const 
     float a = 0.f;
     for (int f = 0; f < nb; ++f) a = fmaf(mag[f], mel_t[f * n_mels + m], a);
     a = fmaxf(a, eps);
-    o[m] = log_mode == 10 ? log10f(a) : (log_mode == 2 ? log2f(a) : logf(a));
+    o[m] = log_base(a, log_mode);
   }
 }
 
@@ -193,6 +213,7 @@ void srn_zero_u32(unsigned* p, const int n, hipStream_t stream) {
 extern "C" int srn_pad_signal(const float* x, float* out, int B, int n, int pad, int ld, int mode, void* stream) {
   SRN_CHECK_ARG(x && out && B > 0 && n > 1 && pad >= 0 && ld >= n + 2 * pad && (mode == 0 || mode == 1),
                 "pad_signal: bad args");
+  SRN_CHECK_ARG(B <= 65535, "pad_signal: B %d is above the limit of 65535", B);
   SRN_CHECK_ARG(mode == 1 || pad < n, "pad_signal: reflect padding of %d needs more than %d samples", pad, n);
   int bx = (ld + 255) / 256;
   bx = bx > 4096 ? 4096 : bx;
@@ -216,6 +237,7 @@ extern "C" int srn_loudness(const float* spec, const float* a_weight_db, unsigne
                             int frames, int n_bins, int ld, float amin, float top_db, float add_eps, void* stream) {
   SRN_CHECK_ARG(spec && a_weight_db && gmax_ws && out && B > 0 && frames > 0 && n_bins > 0 && ld >= 2 * n_bins,
                 "loudness: bad args");
+  SRN_CHECK_ARG(B <= 65535, "loudness: B %d is above the limit of 65535", B);
   hipStream_t st = (hipStream_t)stream;
   srn_zero_u32(gmax_ws, B, st);
   hipLaunchKernelGGL(power_max_kernel, dim3(frames < 512 ? frames : 512, B), dim3(256), 0, st, spec, gmax_ws, frames,

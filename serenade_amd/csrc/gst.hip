@@ -71,6 +71,8 @@ extern "C" int srn_style_token_attention_kv(const float* ref, const float* wq_t,
   SRN_CHECK_ARG(ref && wq_t && bq && k && v && wo_t && bo && out, "style_token_attention_kv: null");
   SRN_CHECK_ARG(B > 0 && F > 0 && n_head > 0 && F % n_head == 0 && n_tok > 0 && Dq > 0,
                 "style_token_attention_kv: bad sizes");
+  // token_scores_softmax normalises head h in thread h of the workgroup of 256
+  SRN_CHECK_ARG(n_head <= 256, "style_token_attention_kv: n_head %d is above the limit of 256", n_head);
   const size_t smem = (size_t)(2 * F + n_head * n_tok + Dq) * sizeof(float);
   SRN_CHECK_ARG(smem <= 64 * 1024, "style_token_attention_kv: too large for LDS");
   hipLaunchKernelGGL(style_token_attention_kv_kernel, dim3(B), dim3(256), smem, (hipStream_t)stream, ref, wq_t, bq, k,

@@ -38,6 +38,9 @@ def emul_features(name, a):
         sv, ov = _tview(spec, B, T, ld, T * ld), _tview(out, B, T, 1, T)[..., 0]
         for b in range(B):
             L = min(int(frames[b]), T)
+            if L <= 0:  # no frame of its own: no maximum to take
+                ov[b] = 0
+                continue
             p = sv[b, :L, :nb] ** 2 + sv[b, :L, nb:2 * nb] ** 2
             db = 10 * torch.log10(torch.clamp(p, min=amin))
             db = torch.maximum(db, db.max() - top_db) + aw
@@ -75,6 +78,53 @@ def test_items_do_not_see_each_other(emulated):
 
 def test_all_lengths_full_is_the_dense_call(emulated):
     C.check_anchored_to_dense(CPU)
+
+
+@pytest.mark.parametrize("geom", list(C.GEOMETRIES), ids=lambda g: "fft{}-hop{}-win{}-mels{}".format(*g))
+def test_geometry_logmel_meets_the_oracle(emulated, geom):
+    """dense and ragged at a geometry that gives the STFT plan another shape; the emulator keeps to a quarter of the
+    bound, which is four times what it measured"""
+    fft, hop, win, _ = geom
+    n = C.geometry_lengths(fft, hop)[0]
+    assert C.plan_shape(features._Stft(CPU, 1, n, fft, hop, win)) == C.GEOMETRIES[geom]
+    C.check_geometry("mel", geom, C.geometry_mel_errors(geom, CPU), share=0.25, own=False)
+
+
+@pytest.mark.parametrize("mode", C.PAD_MODES)
+@pytest.mark.parametrize("hop", list(C.LOUD_HOPS))
+def test_geometry_loudness_meets_the_oracle(emulated, hop, mode):
+    n = C.geometry_lengths(C.LOUD_FFT, hop)[0]
+    assert C.plan_shape(features._Stft(CPU, 1, n, C.LOUD_FFT, hop, C.LOUD_FFT, mode)) == C.LOUD_HOPS[hop]
+    C.check_geometry("loud", (hop, mode), C.geometry_loud_errors(hop, mode, CPU), share=0.25)
+
+
+def test_geometries_reach_the_plan_branches_they_are_listed_for(emulated):
+    """so that a change of features._Stft cannot empty the list without anyone noticing"""
+    from tests._rowop_cases import _round_up
+    shapes = set(C.GEOMETRIES.values()) | set(C.LOUD_HOPS.values())
+    assert {c for c, _, _ in shapes} == {4, 8, 16}
+    assert {(c, cw) for c, cw, _ in shapes} == {(4, 4), (8, 8), (16, 32)}      # cw = c: the generic contraction kernel
+    assert {g for _, _, g in shapes} >= {1, 2, 4, 8}                             # one group; more than two chained
+    assert C.GEOMETRIES[(1024, 256, 1024, 80)] == C.plan_shape(features._Stft(CPU, 1, 2321, 1024, 256, 1024))  # defaults
+    assert C.GEOMETRIES[(64, 16, 64, 130)][2] == 1 and 64 // 32 == 2            # a single group of 2 taps
+    assert C.GEOMETRIES[(512, 128, 400, 128)][2] == 1 and 512 // 32 == features._lib.SRN_MAX_TAPS
+    assert any(m > 128 for _, _, _, m in C.GEOMETRIES) and any(m > 1 + f // 2 for f, _, _, m in C.GEOMETRIES)
+    assert any((f - w) % 2 for f, _, w, _ in C.GEOMETRIES)                      # an odd window difference
+    assert C.empty_filters((512, 100, 401, 160)) > 0 and C.empty_filters((1024, 256, 1024, 80)) == 0
+    for what, (base, bound) in C.GEOM_TOL.items():
+        assert abs(bound - _round_up(4 * base)) <= 1e-9 * bound, what
+    assert C.GEOM_TOL["mel"][1] <= C.TOL and C.GEOM_TOL["loud"][1] <= C.TOL
+    for geom, (base, bound) in C.GEOM_OWN.items():  # derived the same way, from the sum in the contraction's order
+        assert f"{C.kernel_order_baseline(geom):.3e}" == f"{base:.3e}" and abs(bound - _round_up(4 * base)) <= 1e-9 * bound
+        assert geom in C.GEOMETRIES
+    n_ill, where = 0, set()
+    for geom in C.GEOMETRIES:
+        ns = C.geometry_lengths(geom[0], geom[1])
+        for n, seed in ((ns[0], 30), (ns[0], 31), (ns[1], 32), (ns[2], 33)):
+            k = int((C.mel_conditioning(C.wave(n, seed), geom) > C.ILL_COND).sum())
+            n_ill += k
+            where |= {(geom, n)} if k else set()
+    assert n_ill == 2 and where == {((512, 100, 401, 160), 911)}  # the own bound covers two elements, no more
 
 
 def test_without_lengths_the_result_is_a_bare_tensor(emulated):
