@@ -306,6 +306,14 @@ int srn_hifigan_resunit_ragged_route(const SrnResUnitParams* p, const int32_t* l
  * out (B, T, 3C) = [lrelu(x[t]) | lrelu(x[t - r]) | lrelu(x[t + r])], r = rint(d[b, t] * dilation), zero outside. */
 int srn_pd_gather(const float* x, const float* d, float* out, int B, int T, int C, float dilation, float slope,
                   void* stream);
+/* The same gather over a ragged batch: item b holds L_b = min(lens[b], T) rows (lens: device, B int32, each >= 1; x, d
+ * and out keep their (B, T, ...) strides).  out[b, t] for t < L_b is bit for bit what srn_pd_gather gives for that item
+ * alone (B = 1, T = L_b): r comes from the item's own d[b, t], the neighbours t -+ r are valid inside [0, L_b) only and
+ * zero outside.  Rows t >= L_b of x and d are not loaded, whatever they hold (NaN included); rows t >= L_b of out are
+ * not written -- the kernel's loop runs over L_b * C / 4, dead rows cost nothing.  Argument checks as the dense call,
+ * plus a non-NULL `lens`. */
+int srn_pd_gather_ragged(const float* x, const float* d, const int32_t* lens, float* out, int B, int T, int C,
+                         float dilation, float slope, void* stream);
 
 /* GST style encoder (serenade/modules/gst/style_encoder.py:142-191,235-252).  Its Conv2d(k3, s2, p1) + BatchNorm2d(eval)
  * + ReLU layers are srn_conv_gemm launches (one stride-2 three-tap contraction along the mel axis per kernel row, BatchNorm

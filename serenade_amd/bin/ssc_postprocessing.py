@@ -10,7 +10,9 @@ hydra itself is not needed).  For every `*.wav` under in_dir whose name contains
 transposed F0 contour is read from the `lf0` dataset the decode CLI left beside it (`.h5`, or `.npz` where h5py is
 unavailable), the waveform is re-analysed (serenade_amd.world.Analyzer: CheapTrick -> mel-cepstrum, D4C -> band
 aperiodicity, continuous F0, dilated factors, sine excitation) and `NAME_sifigan.wav` (PCM_16) is written next to it.
-Files without an F0 contour or without a voiced frame are skipped, as in the reference.
+Files without an F0 contour or without a voiced frame are skipped, as in the reference.  `batch_utterances=N` takes the
+files N at a time: one analysis call on the padded batch and one ragged generator call per group (lengths as data,
+DESIGN.md 7j), the same files for the same `seed` as the default one-by-one loop.
 
 A wav at another rate than `sample_rate` is resampled on the GPU as the reference does with librosa (:146), in float64
 on the samples as read (`load_wave`, serenade_amd.audio.resample: DESIGN.md 7e states how far that filter and soxr's
@@ -37,7 +39,7 @@ DEFAULTS = {
     "in_dir": None, "out_dir": None, "stats": None, "checkpoint_path": None, "f0_factors": [1.00], "seed": 100,
     "sample_rate": 24000, "frame_period": 5, "f0_floor": 100, "f0_ceil": 840, "mcep_dim": 39, "mcap_dim": 19,
     "aux_feats": ["mcep", "bap"], "dense_factors": [0.5, 1, 4, 8], "df_f0_type": "cf0", "sine_amp": 0.1,
-    "noise_amp": 0.003, "sine_f0_type": "cf0", "signal_types": ["sine"],
+    "noise_amp": 0.003, "sine_f0_type": "cf0", "signal_types": ["sine"], "batch_utterances": 1,
     "generator": {k: (list(v) if isinstance(v, tuple) else copy.deepcopy(v)) for k, v in sifigan.DEFAULT_PARAMS.items()},
 }
 GENERATORS = ("sifigan",)
@@ -62,6 +64,8 @@ def parse_overrides(argv):
         if leaf not in node:
             raise SystemExit(f"unknown option {key!r}")
         node[leaf] = yaml.safe_load(text) if text != "" else None
+    if type(cfg["batch_utterances"]) is not int or cfg["batch_utterances"] < 1:
+        raise SystemExit(f"batch_utterances={cfg['batch_utterances']!r}: expected an integer >= 1")
     return cfg
 
 
@@ -129,6 +133,62 @@ class PostJob:
         write_wav_pcm16(wav_file[:-len(".wav")] + "_sifigan.wav", y.view(-1).cpu().numpy(), self.cfg["sample_rate"])
         return c.size(-1)
 
+    def process_group(self, wav_files):
+        """`wav_files` through ONE analysis call and ONE ragged generator call.  The noise is drawn as process() draws
+        it -- one torch.randn((1, 1, n_b)) per analysed file, in order, between the features and the excitation -- so
+        both paths consume the generator identically.  A file without an F0 contour or one that fails to load is
+        skipped alone; if the analysis refuses the group, its files go one by one."""
+        items = []
+        for wav_file in wav_files:
+            logger.info(f"Start processing {wav_file}")
+            try:  # an unreadable contour or wav is skipped alone, as run()'s loop skips it
+                f0 = self.f0_of(wav_file)
+                if f0 is None:
+                    print(f"No h5 file containing f0 found for {wav_file}")
+                    continue
+                items.append((wav_file, load_wave(wav_file, self.cfg["sample_rate"], self.device), np.asarray(f0)))
+            except (ValueError, NotImplementedError, OSError) as e:
+                logger.error(f"skipped {wav_file}: {e}")
+        if not items:
+            return 0
+        lengths = [w.size(1) for _, w, _ in items]
+        wave = torch.zeros(len(items), max(lengths), dtype=torch.float32, device=self.device)
+        for b, (_, w, _) in enumerate(items):
+            wave[b, :w.size(1)] = w[0]
+        an = self.analyzer
+        try:
+            feats = an.features(wave, lengths, [f0 for _, _, f0 in items])
+        except (ValueError, NotImplementedError) as e:  # nothing drawn yet: the one-by-one loop finds the bad file
+            logger.error(f"group of {len(items)} not analysed together ({e}); processing its files one by one")
+            frames = 0
+            for wav_file, _, _ in items:
+                try:
+                    frames += self.process(wav_file)
+                except (ValueError, NotImplementedError, OSError) as e1:
+                    logger.error(f"skipped {wav_file}: {e1}")
+            return frames
+        n_frames = feats["n_frames"]
+        noise = None
+        if an.noise_amp > 0:
+            noise = torch.zeros(len(items), 1, max(n_frames) * an.hop, dtype=torch.float32, device=self.device)
+            for b, nf in enumerate(n_frames):
+                noise[b, :, :nf * an.hop] = torch.randn((1, 1, nf * an.hop), device=self.device)
+        in_signal, dfs = an.excitation(feats, noise)
+        ok = feats["ok"].tolist()
+        for (wav_file, _, _), good in zip(items, ok):
+            if not good:
+                logger.warning(f"{wav_file}: all of the f0 values are 0.")
+        if not any(ok):
+            return 0
+        y = self.model(in_signal, feats["c"], dfs, lengths=n_frames)[0]  # items are independent: a silent one is dropped
+        frames = 0
+        for b, (wav_file, _, _) in enumerate(items):
+            if ok[b]:
+                write_wav_pcm16(wav_file[:-len(".wav")] + "_sifigan.wav",
+                                y[b, 0, :n_frames[b] * self.model.hop].cpu().numpy(), self.cfg["sample_rate"])
+                frames += n_frames[b]
+        return frames
+
     def run(self):
         rank, n_ranks = parallel.rank_world()
         files = self.files()
@@ -139,13 +199,22 @@ class PostJob:
             if self.cfg[key] != DEFAULTS[key]:
                 logger.warning(f"{key}={self.cfg[key]} has no effect here: the F0 comes from the decode CLI's lf0 and `mcap` "
                                "is never consumed with aux_feats [mcep, bap] (ssc_postprocessing.py:147-170)")
+        n_group = self.cfg["batch_utterances"]
         with torch.no_grad():
-            for wav_file in files[lo:hi]:
-                logger.info(f"Start processing {wav_file}")
-                try:
-                    frames += self.process(wav_file)
-                except (ValueError, NotImplementedError, OSError) as e:  # one bad file must not end the directory run
-                    logger.error(f"skipped {wav_file}: {e}")
+            if n_group > 1:  # N files per analysis call and ragged generator call
+                for g0 in range(lo, hi, n_group):
+                    group = files[g0:min(g0 + n_group, hi)]
+                    try:
+                        frames += self.process_group(group)
+                    except (ValueError, NotImplementedError, OSError) as e:  # nor must one bad group
+                        logger.error(f"skipped {len(group)} files from {group[0]}: {e}")
+            else:
+                for wav_file in files[lo:hi]:
+                    logger.info(f"Start processing {wav_file}")
+                    try:
+                        frames += self.process(wav_file)
+                    except (ValueError, NotImplementedError, OSError) as e:  # one bad file must not end the directory run
+                        logger.error(f"skipped {wav_file}: {e}")
         torch.cuda.synchronize()
         dt = max(time.time() - t0, 1e-9)
         logger.info(f"rank {rank}/{n_ranks}: {frames} analysis frames in {dt:.2f} s = {frames / dt:.1f} frames/s")

@@ -624,13 +624,22 @@ extern "C" int srn_out_conv_tanh_ragged(const float* x, const float* w, const fl
 //   out[b, t, 0:C]   = lrelu(x[b, t])
 //   out[b, t, C:2C]  = lrelu(x[b, t - r]),  out[b, t, 2C:3C] = lrelu(x[b, t + r]),   r = rint(d[b, t] * dilation)
 // (zero outside the signal).  Whole 128-B+ channel rows move as float4; one wave handles several rows.
+// One kernel text, two instances (as the output stage above).  Dense (RAGGED = false, no `lens` argument: arguments and
+// code as before the ragged entry point existed, L folds to T).  Ragged (RAGGED = true, one trailing argument: the
+// per-item lengths, srn_pd_gather_ragged): item b is the dense B = 1 call at T = L_b = min(lens[b], T) -- "outside the
+// signal" is outside [0, L_b), and the grid-stride loop runs over L_b * C / 4: rows t >= L_b of x and d are not loaded
+// (so no NaN there reaches rintf or a select), rows t >= L_b of out are not written.  L_b is one uniform scalar load.
 namespace {
+template <bool RAGGED = false, class... Lens>
 __global__ __launch_bounds__(256) void pd_gather_kernel(const float* __restrict__ x, const float* __restrict__ d,
                                                         float* __restrict__ out, int T, int C, float dilation,
-                                                        float slope) {
+                                                        float slope, const Lens... lens) {
+  static_assert(sizeof...(Lens) == (RAGGED ? 1 : 0), "the ragged instance takes the lengths, the dense one nothing");
   const int b = blockIdx.y;
   const int c4n = C / 4;
-  const int64_t total = (int64_t)T * c4n;
+  int L = T;
+  if constexpr (RAGGED) L = max(min(srn_first(lens...)[b], T), 0);
+  const int64_t total = (int64_t)L * c4n;
   const float* xb = x + (int64_t)b * T * C;
   float* ob = out + (int64_t)b * T * 3 * C;
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
@@ -640,8 +649,8 @@ __global__ __launch_bounds__(256) void pd_gather_kernel(const float* __restrict_
     const int tp = t - r, tf = t + r;
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 v0 = *reinterpret_cast<const float4*>(xb + (int64_t)t * C + c);
-    float4 vp = (tp >= 0 && tp < T) ? *reinterpret_cast<const float4*>(xb + (int64_t)tp * C + c) : z;
-    float4 vf = (tf >= 0 && tf < T) ? *reinterpret_cast<const float4*>(xb + (int64_t)tf * C + c) : z;
+    float4 vp = (tp >= 0 && tp < L) ? *reinterpret_cast<const float4*>(xb + (int64_t)tp * C + c) : z;
+    float4 vf = (tf >= 0 && tf < L) ? *reinterpret_cast<const float4*>(xb + (int64_t)tf * C + c) : z;
     auto lr = [slope](float4 v) {
       v.x = v.x > 0.f ? v.x : v.x * slope;
       v.y = v.y > 0.f ? v.y : v.y * slope;
@@ -662,8 +671,19 @@ extern "C" int srn_pd_gather(const float* x, const float* d, float* out, int B, 
   SRN_CHECK_ARG(x && d && out && B > 0 && T > 0 && C > 0 && C % 4 == 0, "pd_gather: bad args");
   int64_t blocks = ((int64_t)T * (C / 4) + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(pd_gather_kernel, dim3((unsigned)blocks, B), dim3(256), 0, (hipStream_t)stream, x, d, out, T, C,
-                     dilation, slope);
+  hipLaunchKernelGGL((pd_gather_kernel<>), dim3((unsigned)blocks, B), dim3(256), 0, (hipStream_t)stream, x, d, out, T,
+                     C, dilation, slope);
+  SRN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int srn_pd_gather_ragged(const float* x, const float* d, const int32_t* lens, float* out, int B, int T,
+                                    int C, float dilation, float slope, void* stream) {
+  SRN_CHECK_ARG(x && d && lens && out && B > 0 && T > 0 && C > 0 && C % 4 == 0, "pd_gather_ragged: bad args");
+  int64_t blocks = ((int64_t)T * (C / 4) + 255) / 256;  // sized by the capacity: the lengths are device data
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL((pd_gather_kernel<true, SrnLens>), dim3((unsigned)blocks, B), dim3(256), 0, (hipStream_t)stream,
+                     x, d, out, T, C, dilation, slope, lens);
   SRN_CHECK_LAUNCH();
   return 0;
 }

@@ -486,6 +486,14 @@ def pd_gather_op(x, d, out, B, T, C, dilation, slope):
     return CallOp("srn_pd_gather", (x, d, out, B, T, C, float(dilation), float(slope)))
 
 
+def pd_gather_ragged_op(x, d, lens, out, B, T, C, dilation, slope):
+    """pd_gather_op over a ragged batch: lens (B,) int32 rows per item; rows past an item's end are neither read nor
+    written"""
+    if lens.dtype != torch.int32:
+        raise TypeError("pd_gather_ragged_op: lens must be int32")
+    return CallOp("srn_pd_gather_ragged", (x, d, lens, out, B, T, C, float(dilation), float(slope)))
+
+
 def gru_recur_last_op(gi, w_hh_t, b_hh, h, B, T, H):
     return CallOp("srn_gru_recur_last", (gi, w_hh_t, b_hh, h, B, T, H))
 

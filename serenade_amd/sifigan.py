@@ -17,10 +17,10 @@ from collections import OrderedDict
 
 import torch
 
-from . import _shapes, ops
+from . import _shapes, ops, vocoder
 from .models import _Packed, _fold_wn
 from .ops import ACT_LEAKY, POST_DIV, POST_LEAKY, RES_ADD
-from .plan import conv_op, dev_f32, require_cuda as _require_cuda, rup
+from .plan import conv_op, dev_f32, item_lengths, lru_get, require_cuda as _require_cuda, rup
 
 DEFAULT_PARAMS = dict(
     in_channels=43, out_channels=1, channels=512, kernel_size=7, upsample_scales=(5, 4, 3, 2),
@@ -76,6 +76,7 @@ class SiFiGANGenerator(_Packed):
         for s, k in zip(cfg["upsample_scales"], cfg["upsample_kernel_sizes"]):
             assert k == 2 * s
         super().__init__(sifigan_shapes(**cfg))
+        self._ragged_plans = {}
         self.cfg = cfg
         self.slope = float(cfg["nonlinear_activation_params"].get("negative_slope", 0.1))
         self.hop = 1
@@ -159,21 +160,76 @@ class SiFiGANGenerator(_Packed):
             self._plans[key] = SiFiGANPlan(self, B, T)
         return self._plans[key]
 
+    def _invalidate(self):
+        super()._invalidate()
+        self._ragged_plans = {}  # a cache of its own: a miss in plan() clears _plans, never these
+
+    def plan_ragged(self, B, T_max, bucket=None):
+        """the ragged plan for B items of at most T_max frames: its capacity is T_max rounded up to `bucket` frames
+        (RAGGED_BUCKET), so one plan serves every batch of B whose longest item falls in the same bucket"""
+        T_cap = rup(T_max, vocoder.RAGGED_BUCKET if bucket is None else int(bucket))
+        key = (B, T_cap, ops.DEFAULT_PRECISION)
+        return lru_get(self._ragged_plans, key, 4, lambda: RaggedSiFiGANPlan(self, B, T_cap))
+
     @torch.no_grad()
-    def forward(self, x, c, d):
+    def forward(self, x, c, d, lengths=None):
         """x (B, 1, T*hop) sine excitation, c (B, in_channels, T), d: list of (B, 1, T*cumprod(scales)[i]) dilation
-        factors -> (waveform (B, 1, T*hop), excitation (B, 1, T*hop))."""
+        factors -> (waveform (B, 1, T*hop), excitation (B, 1, T*hop)).  lengths (B frame counts in [1, T]): the batch is
+        ragged -- item b is computed as its own B = 1 call on its first lengths[b] frames (the rows of x, c and d behind
+        them may hold anything) and both outputs are zero past lengths[b] * hop."""
         _require_cuda(c, "SiFiGANGenerator.forward")
         B, _, T = c.shape
+        if lengths is not None:
+            lengths = item_lengths(lengths, B, T, "SiFiGANGenerator.forward")
+            pl = self._run_ragged(B, T, lengths, lambda pl: pl.load_batch(x, c, d))
+            return pl.wave[:, :T * self.hop].clone().unsqueeze(1), pl.exc[:, :T * self.hop].clone().unsqueeze(1)
         pl = self.plan(B, T)
         pl.load(x, c, d)
         pl.run()
         return pl.wave.clone().unsqueeze(1), pl.exc.clone().view(B, 1, -1)
 
+    @torch.no_grad()
+    def inference_ragged(self, items):
+        """[(x_b (1, 1, T_b*hop), c_b (1, in_channels, T_b), [d_bi (1, 1, T_b*cumprod(scales)[i])])] ->
+        [(waveform (T_b*hop,), excitation (T_b*hop,))]: utterances of different lengths in ONE call, each computed as
+        its own B = 1 forward."""
+        items = list(items)
+        if not items:
+            raise ValueError("SiFiGANGenerator.inference_ragged: no items")
+        for x, c, d in items:
+            _require_cuda(c, "SiFiGANGenerator.inference_ragged")
+        lengths = item_lengths([c.shape[-1] for _, c, _ in items], len(items), max(c.shape[-1] for _, c, _ in items),
+                               "SiFiGANGenerator.inference_ragged")
+
+        def fill(pl):
+            for b, (x, c, d) in enumerate(items):
+                pl.load_item(b, x, c, d)
+        pl = self._run_ragged(len(items), max(lengths), lengths, fill)
+        return [(pl.wave[b, :n * self.hop].clone(), pl.exc[b, :n * self.hop].clone()) for b, n in enumerate(lengths)]
+
+    def _run_ragged(self, B, T_max, lengths, fill):
+        """run the ragged plan of (B, T_max): `fill(plan)` writes the items into the plan's input buffers (rows past an
+        item's end keep whatever an earlier batch left there: they are never read as data); returns the plan, whose
+        wave / exc hold the result until its next run"""
+        pl = self.plan_ragged(B, T_max)
+        pl.set_lengths(lengths)
+        fill(pl)
+        pl.run()
+        return pl
+
 
 class SiFiGANPlan:
     def __init__(self, gen, B, T):
+        self._build(gen, B, T, None)
+
+    def _build(self, gen, B, T, lens):
+        """the walk of the dense plan and of RaggedSiFiGANPlan.  lens: None, or one (B,) int32 device tensor per rate --
+        lens[0] for the analysis frames, lens[i + 1] behind upsample i, lens[-1] the final (waveform) rate -- which makes
+        every length data: each conv gets the lengths of the buffer it reads as len_in (rows at or past them read as the
+        zeros an item alone would be padded with), the gather and the output stage run their ragged entry points and the
+        excitation's conv zeroes its own tail (len_out)."""
         P, cfg = gen.packed(), gen.cfg
+        masked = (lambda st: {}) if lens is None else (lambda st: {"len_in": lens[st]})
         dev = gen._device()
         slope = gen.slope
         f = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
@@ -201,17 +257,17 @@ class SiFiGANPlan:
 
         conv = functools.partial(conv_op, B)
         h = f(B, T, C0)
-        ol.append(conv(c_cl, cin_p, T, P["in_w"], P["in_b"], h, C0, T, ops.conv_taps(ks)))
+        ol.append(conv(c_cl, cin_p, T, P["in_w"], P["in_b"], h, C0, T, ops.conv_taps(ks), **masked(0)))
 
         def down(net, first):
             """first: (B, Rf, Cl) feature at the final rate -> list of features down to the first stage's rate"""
             feats = [first]
             cur, rc = first, Rf
-            for dn in P[net + "_down"]:
+            for j, dn in enumerate(P[net + "_down"]):  # conv j reads the rate behind upsample n - 1 - j: its lengths
                 ro = rc // dn["s"]
                 o = f(B, ro, dn["cout"])
                 ol.append(conv(cur, dn["cin"], rc, dn["w"], dn["b"], o, dn["cout"], ro, dn["taps"], in_stride=dn["s"],
-                               post=POST_LEAKY, post_div=slope))
+                               post=POST_LEAKY, post_div=slope, **masked(n - j)))
                 feats.append(o)
                 cur, rc = o, ro
             return feats
@@ -219,36 +275,42 @@ class SiFiGANPlan:
         def up(net, i, src, csrc, rsrc, emb, out):
             u = P[net + "_up"][i]
             s, co, ro = u["s"], u["cout"], rsrc * u["s"]
-            for ph, (taps, wp) in enumerate(u["phases"]):
+            for ph, (taps, wp) in enumerate(u["phases"]):  # a phase reads the stage below: its lengths
                 ol.append(conv(src, csrc, rsrc, wp, u["b"], out, co, rsrc, taps, pro_act=ACT_LEAKY, pro_slope=slope,
                                out_bs=ro * co, out_t_stride=s, out_t_off=ph, res=emb, res_mode=RES_ADD,
-                               res_bs=ro * co, ld_res=co))
+                               res_bs=ro * co, ld_res=co, **masked(i)))
 
         # ---- source network
         emb0 = f(B, Rf, Cl)
-        ol.append(conv(x_cl, 4, Rf, P["emb_w"], P["emb_b"], emb0, Cl, Rf, ops.conv_taps(ks)))
+        ol.append(conv(x_cl, 4, Rf, P["emb_w"], P["emb_b"], emb0, Cl, Rf, ops.conv_taps(ks), **masked(n)))
         embs = down("sn", emb0)
         e_a, e_b, g3, xt = f(B * big), f(B * big), f(B * 3 * big), f(B * big)
         cur, ccur, rcur = h, C0, T
         for i in range(n):
             C, R = Cs[i], Rs[i]
+            here = masked(i + 1)
             x_, y_ = (e_a, e_b) if cur is not e_a else (e_b, e_a)  # never up-sample a buffer onto itself
             up("sn", i, cur, ccur, rcur, embs[-i - 1], x_)
             for blk in P["sn_blocks"][i]:
-                ol.append(ops.pd_gather_op(x_, self.d[i], g3, B, R, C, blk["dil"], slope))
+                if lens is None:
+                    ol.append(ops.pd_gather_op(x_, self.d[i], g3, B, R, C, blk["dil"], slope))
+                else:  # g3 rows past an item's end keep what they held: the GEMM behind reads them as zero
+                    ol.append(ops.pd_gather_ragged_op(x_, self.d[i], lens[i + 1], g3, B, R, C, blk["dil"], slope))
                 if "wa" in blk:
-                    ol.append(conv(g3, 3 * C, R, blk["w3"], blk["b3"], xt, C, R, [0]))
+                    ol.append(conv(g3, 3 * C, R, blk["w3"], blk["b3"], xt, C, R, [0], **here))
                     ol.append(conv(xt, C, R, blk["wa"], blk["ba"], y_, C, R, ops.conv_taps(3), pro_act=ACT_LEAKY,
-                                   pro_slope=slope, res=x_, res_mode=RES_ADD, res_bs=R * C, ld_res=C))
+                                   pro_slope=slope, res=x_, res_mode=RES_ADD, res_bs=R * C, ld_res=C, **here))
                 else:
                     ol.append(conv(g3, 3 * C, R, blk["w3"], blk["b3"], y_, C, R, [0], res=x_, res_mode=RES_ADD,
-                                   res_bs=R * C, ld_res=C))
+                                   res_bs=R * C, ld_res=C, **here))
                 x_, y_ = y_, x_
             cur, ccur, rcur = x_, C, R
         e_fin = f(B, Rf, Cl)
         ol.append(ops.copy_channels_op(cur, Rf * Cl, Cl, 0, e_fin, Rf * Cl, Cl, 0, B, Rf, Cl))
         self.exc = f(B, Rf)
-        ol.append(conv(e_fin, Cl, Rf, P["sn_out_w"], P["sn_out_b"], self.exc, 1, Rf, ops.conv_taps(ks)))
+        # ragged: len_out makes the conv store 0 at rows past an item's end (a select in the kernel's epilogue)
+        ol.append(conv(e_fin, Cl, Rf, P["sn_out_w"], P["sn_out_b"], self.exc, 1, Rf, ops.conv_taps(ks), **masked(n),
+                       **({} if lens is None else {"len_out": lens[n]})))
         # ---- filter network
         fembs = down("fn", e_fin)
         u_, p0, p1, acc = f(B * big), f(B * big), f(B * big), f(B * big)
@@ -257,6 +319,7 @@ class SiFiGANPlan:
         cur, ccur, rcur = h, C0, T
         for i in range(n):
             C, R = Cs[i], Rs[i]
+            here = masked(i + 1)
             up("fn", i, cur, ccur, rcur, fembs[-i - 1], u_)
             for j in range(nb):
                 convs = P["fn_blocks"][i * nb + j]
@@ -273,11 +336,15 @@ class SiFiGANPlan:
                             fin.update(post=POST_DIV, post_div=float(nb))
                     ol.append(conv(x_, C, R, cv["w"], cv["b"], dst, C, R, ops.conv_taps(cv["k"], cv["d"]),
                                    pro_act=ACT_LEAKY, pro_slope=slope, res=x_, res_mode=RES_ADD, res_bs=R * C,
-                                   ld_res=C, **fin))
+                                   ld_res=C, **fin, **here))
                     x_ = dst
             cur, ccur, rcur = acc, C, R
         self.wave = f(B, Rf)
-        ol.append(ops.out_conv_tanh_op(cur, P["fn_out_w"], P["fn_out_b"], self.wave, B, Rf, Cl, ks, slope))
+        if lens is None:
+            ol.append(ops.out_conv_tanh_op(cur, P["fn_out_w"], P["fn_out_b"], self.wave, B, Rf, Cl, ks, slope))
+        else:
+            ol.append(ops.out_conv_tanh_ragged_op(cur, P["fn_out_w"], P["fn_out_b"], self.wave, lens[n], B, Rf, Cl, ks,
+                                                  slope))
         self.ops = ol
 
     def load(self, x, c, d):
@@ -289,3 +356,49 @@ class SiFiGANPlan:
     def run(self):
         for op in self.ops:
             op()
+
+
+class RaggedSiFiGANPlan(SiFiGANPlan):
+    """SiFiGANPlan with the lengths as data: one plan (and one captured graph) for every batch of B items whose longest
+    has at most T_cap frames.  Inputs (load_item / load_batch): rows at or past an item's length may hold anything;
+    outputs: self.wave and self.exc (B, T_cap * hop), zero past each item's end.  Item b is computed as its own B = 1
+    dense plan of lengths[b] frames computes it.  self.lens (n_stages + 1, B) int32 holds the per-rate lengths the ops
+    read when they run: set_lengths() rewrites it in place -- outside the captured graph, whose nodes only carry its
+    address."""
+
+    def __init__(self, gen, B, T_cap):
+        self.scales = [1]
+        for s in gen.cfg["upsample_scales"]:
+            self.scales.append(self.scales[-1] * s)
+        self.lens = torch.zeros(len(self.scales), B, dtype=torch.int32, device=gen._device())
+        self._build(gen, B, T_cap, list(self.lens.unbind(0)))
+        self._runner = ops.GraphRunner(lambda: self.ops)
+
+    def set_lengths(self, lengths):
+        """lengths: B frame counts in [1, T_cap] (validated by the caller, plan.item_lengths)"""
+        host = torch.tensor([[int(n) * s for n in lengths] for s in self.scales], dtype=torch.int32)
+        self.lens.copy_(host)
+
+    def load_item(self, b, x, c, d):
+        """item b: x (..., T_b * hop), c (in_ch, T_b) or (1, in_ch, T_b), d[i] (..., T_b * cumprod(scales)[i]) into the
+        front of its rows; what lies behind them stays as it was"""
+        c = c.reshape(c.shape[-2], c.shape[-1])
+        self._c_in[b, :, :c.shape[1]].copy_(c)
+        x = x.reshape(-1)
+        self._x_in[b, :x.numel()].copy_(x)
+        for buf, di in zip(self.d, d):
+            di = di.reshape(-1)
+            buf[b, :di.numel()].copy_(di)
+
+    def load_batch(self, x, c, d):
+        """the (B, ., T) tensors of a forward(lengths=) call, T <= T_cap, into the front of every item's rows"""
+        T = c.shape[2]
+        self._c_in[:, :, :T].copy_(c)
+        x = x.reshape(self.B, -1)
+        self._x_in[:, :x.shape[1]].copy_(x)
+        for buf, di in zip(self.d, d):
+            di = di.reshape(self.B, -1)
+            buf[:, :di.shape[1]].copy_(di)
+
+    def run(self):
+        self._runner()

@@ -11,10 +11,20 @@ do per frame against the chip's peaks -- they are bound by LDS traffic and barri
               (5 * 6 * 1024 + 2 * 6 * 2048) * 32 B = 1.7 MB of LDS traffic, plus 3 bitonic sorts of 1024 doubles (mostly
               in registers) per voiced frame.
 HBM traffic per frame is 120 new samples in (8 B each, the rest of the window hits L2) and 513 + 3 doubles out.
-Prints one JSON object.  (Values are checked against oracle/world_oracle.py in tests/test_world.py.)"""
+Prints one JSON object.  (Values are checked against oracle/world_oracle.py in tests/test_world.py.)
+
+    worldbench.py B T --ragged      the SiFiGAN generator ONLY, exact fp32, T analysis frames (5 ms), dense against ragged
+                                    (DESIGN.md section 7j): the dense call on equal lengths; the ragged call
+                                    (`forward(lengths=)`) on the same equal lengths; then B DISTINCT lengths per batch
+                                    (8 in 7j's tables), a new set every batch, spread as `vocbench.py --ragged` spreads
+                                    them: (a) the loop of B = 1 dense calls the stage-9 CLI runs without
+                                    batch_utterances (plan build and buffers per new length included), (b) one
+                                    `inference_ragged` call per batch at bucket sizes 1, 32, 64 and 128 frames
+    --graphs / --passes N           as vocbench.py"""
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -106,9 +116,92 @@ def run(B=8, T=1024, dev=None, with_generator=True):
     return out
 
 
+def generator_inputs(B, T, dev, seed=0):
+    """x (B, 1, T * 120) sine excitation, c (B, 43, T), d: the four dilated-factor tracks, as the analysis stage
+    shapes them (values in the range a sung F0 gives)"""
+    rng = np.random.default_rng(seed)
+    scales = sifigan.DEFAULT_PARAMS["upsample_scales"]
+    hop = int(np.prod(scales))
+    c = torch.from_numpy(rng.standard_normal((B, 43, T)).astype(np.float32)).to(dev)
+    f0 = rng.uniform(100, 400, (B, 1, T))
+    x = (0.1 * np.sin(np.cumsum(np.repeat(2 * np.pi * f0 / FS, hop, axis=2), axis=2))).astype(np.float32)
+    d = [torch.from_numpy(np.repeat(FS / f0 / df / 16.0, us, axis=2).astype(np.float32)).to(dev)
+         for df, us in zip((0.5, 1, 4, 8), np.cumprod(scales))]
+    return torch.from_numpy(x).to(dev), c, d
+
+
+def run_ragged(B, T, passes, graphs):
+    """the generator only: dense against ragged"""
+    import serenade_amd
+    from serenade_amd import build, vocoder
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from vocbench import BUCKETS, _timed, distinct_length_sets
+    serenade_amd.set_precision("fp32")
+    ops.set_graphs(graphs)
+    dev = torch.device("cuda:0")
+    g = sifigan.SiFiGANGenerator(**sifigan.DEFAULT_PARAMS)
+    g.load_state_dict(fill_state_dict(_shapes.as_meta(sifigan.sifigan_shapes(**sifigan.DEFAULT_PARAMS)), seed=1))
+    g.remove_weight_norm()
+    g = g.eval().to(dev)
+    x, c, d = generator_inputs(B, T, dev)
+    ups = [t.shape[2] // T for t in d]
+    out = {"build_id": build.built_id(), "graphs": graphs, "passes": passes, "precision": "fp32",
+           "workload": f"SiFiGAN generator, B={B} utterances x {T} frames, hop {g.hop}"}
+
+    def rate(dt, frames):
+        return {"ms_per_batch": dt * 1e3, "frames_per_s": frames / dt}
+
+    def items_of(lens):
+        return [(x[b:b + 1, :, :n * g.hop], c[b:b + 1, :, :n], [t[b:b + 1, :, :n * u] for t, u in zip(d, ups)])
+                for b, n in enumerate(lens)]
+
+    with torch.no_grad():
+        out["dense_equal"] = rate(_timed(lambda: g(x, c, d), 3, 10), B * T)
+        full = [T] * B
+        keep = vocoder.RAGGED_BUCKET  # the entry points take no bucket: the sweep rebinds the default and puts it back
+        try:
+            vocoder.RAGGED_BUCKET = 1  # capacity T exactly: the same rows as the dense call
+            out["ragged_equal"] = rate(_timed(lambda: g(x, c, d, lengths=full), 3, 10), B * T)
+        finally:
+            vocoder.RAGGED_BUCKET = keep
+        out["dense_equal_again"] = rate(_timed(lambda: g(x, c, d), 3, 10), B * T)
+        sets = distinct_length_sets(B, T, passes + 1)
+        sets = sets[-1:] + sets[:-1]  # the warm-up batch is the shortest, so every plan of the passes is new
+        frames = sum(sum(s) for s in sets[1:]) / passes
+
+        def corpus(fn):
+            g._plans.clear()
+            g._ragged_plans.clear()
+            fn(items_of(sets[0]))  # warm-up on lengths no pass reuses
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for s in sets[1:]:
+                fn(items_of(s))
+            torch.cuda.synchronize()
+            return rate((time.perf_counter() - t0) / passes, frames)
+
+        out["distinct_b1_loop"] = corpus(lambda items: [g(*it) for it in items])
+        out["distinct_ragged_call"] = {}
+        try:
+            for bucket in BUCKETS:
+                vocoder.RAGGED_BUCKET = bucket
+                out["distinct_ragged_call"][f"bucket_{bucket}"] = corpus(g.inference_ragged)
+        finally:
+            vocoder.RAGGED_BUCKET = keep
+    return out
+
+
 def main():
-    B, T = (int(v) for v in (sys.argv[1:3] + ["8", "1024"][len(sys.argv) - 1:]))
-    print(json.dumps(run(B, T), indent=1))
+    args = [v for v in sys.argv[1:] if not v.startswith("--")]
+    flags = [v for v in sys.argv[1:] if v.startswith("--")]
+    if set(flags) - {"--ragged", "--graphs", "--passes"} or (flags and "--ragged" not in flags):
+        sys.exit(__doc__)
+    passes = int(args.pop(2)) if "--passes" in flags else 6
+    B, T = (int(v) for v in (args[:2] + ["8", "1024"][len(args):]))
+    if "--ragged" in flags:
+        print(json.dumps(run_ragged(B, T, passes, "--graphs" in flags), indent=1))
+    else:
+        print(json.dumps(run(B, T), indent=1))
 
 
 if __name__ == "__main__":
