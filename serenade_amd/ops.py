@@ -146,17 +146,32 @@ def splitk_workspace(device):
     return _SPLITK_WS[key]
 
 
+def _item_lens(lens, n_batch, what):
+    """the `lens` of a ragged op: an int32 device tensor of (at least) n_batch per-item row counts, read when the op
+    RUNS (a plan rewrites it in place between runs)"""
+    if not (isinstance(lens, torch.Tensor) and lens.dtype == torch.int32 and lens.numel() >= int(n_batch)):
+        raise TypeError(f"{what}: lens must be an int32 tensor of n_batch entries")
+    return lens
+
+
 class ResUnitOp(_StructOp):
-    """A prebuilt srn_hifigan_resunit call: one fused HiFi-GAN residual unit (see include/serenade_hip.h)."""
+    """A prebuilt srn_hifigan_resunit call: one fused HiFi-GAN residual unit (see include/serenade_hip.h).  With `lens`
+    (_item_lens) it is a srn_hifigan_resunit_ragged call of the same struct: item b is computed as its own n_batch = 1,
+    T = lens[b] dense call; rows at or past lens[b] are neither read nor written."""
 
     __slots__ = ("_wplanes",)
     _profiled = True  # timed with the other contraction launches
 
-    def __init__(self, **kw):
-        super().__init__("srn_hifigan_resunit", kw)
+    def __init__(self, lens=None, **kw):
+        if lens is None:
+            super().__init__("srn_hifigan_resunit", kw)
+            return
+        super().__init__("srn_hifigan_resunit_ragged", dict(kw, lens=_item_lens(lens, kw["n_batch"], "ResUnitOp")))
+        entry, lens_p = self._fn, ctypes.c_void_p(_ptr(lens))
+        self._fn = lambda p, stream: entry(p, lens_p, stream)
 
     def _fill(self, *, x, w1, b1, w2, b2, out, n_batch, T, C, k, dilation, slope, res2=None, post_div=0.0,
-               precision=None, route=0, x_bs=None, res2_bs=None, out_bs=None):
+              precision=None, route=0, x_bs=None, res2_bs=None, out_bs=None, lens=None):
         p = SrnResUnitParams()
         p.n_batch, p.T, p.C, p.k, p.dilation, p.slope = int(n_batch), int(T), int(C), int(k), int(dilation), float(slope)
         item = int(T) * int(C)  # batch strides: contiguous items unless given
@@ -172,26 +187,6 @@ class ResUnitOp(_StructOp):
             self._wplanes = (weight_planes(w1, C, k, C, k * C), weight_planes(w2, C, k, C, k * C))
             p.w1_hi, p.w2_hi = self._wplanes[0][0].data_ptr(), self._wplanes[1][0].data_ptr()
         return p
-
-
-class RaggedResUnitOp(_StructOp):
-    """A prebuilt srn_hifigan_resunit_ragged call: ResUnitOp's keywords plus `lens`, the (n_batch,) int32 device tensor
-    of per-item row counts, read when the op RUNS (a plan rewrites it in place between runs).  Item b is computed as
-    its own n_batch = 1, T = lens[b] dense call; rows at or past lens[b] are neither read nor written."""
-
-    __slots__ = ("_wplanes", "_lens")
-    _profiled = True
-
-    def __init__(self, **kw):
-        super().__init__("srn_hifigan_resunit_ragged", kw)
-        entry, lens = self._fn, ctypes.c_void_p(_ptr(self._lens))
-        self._fn = lambda p, stream: entry(p, lens, stream)
-
-    def _fill(self, *, lens, **kw):
-        if not (isinstance(lens, torch.Tensor) and lens.dtype == torch.int32 and lens.numel() >= int(kw["n_batch"])):
-            raise TypeError("RaggedResUnitOp: lens must be an int32 tensor of n_batch entries")
-        self._lens = lens
-        return ResUnitOp._fill(self, **kw)  # the dense op's struct, weight planes included
 
 
 class MultiCopyOp:
@@ -471,26 +466,20 @@ def renorm_op(x, trg_scale, trg_mean, voc_mean, voc_scale, y, rows, C):
     return CallOp("srn_renorm", (x, trg_scale, trg_mean, voc_mean, voc_scale, y, rows, C))
 
 
-def out_conv_tanh_op(x, w, bias, y, B, T, C, k, slope):
-    return CallOp("srn_out_conv_tanh", (x, w, bias, y, B, T, C, k, slope))
-
-
-def out_conv_tanh_ragged_op(x, w, bias, y, lens, B, T, C, k, slope):
-    """out_conv_tanh_op over a ragged batch: lens (B,) int32 rows per item; y is zero past each item's end"""
-    if lens.dtype != torch.int32:
-        raise TypeError("out_conv_tanh_ragged_op: lens must be int32")
+def out_conv_tanh_op(x, w, bias, y, B, T, C, k, slope, lens=None):
+    """lens (_item_lens): a ragged batch, lens[b] rows of item b; y is zero past each item's end"""
+    if lens is None:
+        return CallOp("srn_out_conv_tanh", (x, w, bias, y, B, T, C, k, slope))
+    lens = _item_lens(lens, B, "out_conv_tanh_op")
     return CallOp("srn_out_conv_tanh_ragged", (x, w, bias, y, lens, B, T, C, k, slope))
 
 
-def pd_gather_op(x, d, out, B, T, C, dilation, slope):
-    return CallOp("srn_pd_gather", (x, d, out, B, T, C, float(dilation), float(slope)))
-
-
-def pd_gather_ragged_op(x, d, lens, out, B, T, C, dilation, slope):
-    """pd_gather_op over a ragged batch: lens (B,) int32 rows per item; rows past an item's end are neither read nor
+def pd_gather_op(x, d, out, B, T, C, dilation, slope, lens=None):
+    """lens (_item_lens): a ragged batch, lens[b] rows of item b; rows past an item's end are neither read nor
     written"""
-    if lens.dtype != torch.int32:
-        raise TypeError("pd_gather_ragged_op: lens must be int32")
+    if lens is None:
+        return CallOp("srn_pd_gather", (x, d, out, B, T, C, float(dilation), float(slope)))
+    lens = _item_lens(lens, B, "pd_gather_op")
     return CallOp("srn_pd_gather_ragged", (x, d, lens, out, B, T, C, float(dilation), float(slope)))
 
 

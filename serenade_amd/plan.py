@@ -1,5 +1,6 @@
 """What every plan builder shares: the small helpers, the op builders that several plans repeat (batched conv, dense
-layer, chunked self-attention) and the input / state-dict checks of the waveform front-ends.  A plan is a list of
+layer, chunked self-attention, the stages and the length table of the HiFi-GAN / SiFiGAN generators) and the input /
+state-dict checks of the waveform front-ends.  A plan is a list of
 prebuilt C-ABI calls (``ops.ConvOp`` / ``ops.CallOp``) over preallocated buffers; nothing here launches anything.
 """
 import math
@@ -78,6 +79,88 @@ def linear_op(inp, rows, K, w, b, out, N, **kw):
     """out (rows, N) = inp (rows, K) w^T + b, all rows of a batch as one contraction"""
     return ConvOp(in0=inp, w=w, out=out, n_batch=1, T_in=rows, T_out=rows, C_in=K, N=N, ld_in0=K, ldw=w.shape[1],
                   ld_out=N, bias=b, **kw)
+
+
+# ---------------------------------------------------------------------------------------------- generator stages
+# What the HiFi-GAN and SiFiGAN plans share (vocoder.py, sifigan.py).  Lengths are optional everywhere: None makes the
+# dense plan; a (B,) int32 device tensor makes the length data -- a conv reads rows at or past its input's length as the
+# zeros an item alone would be padded with (len_in), the fused unit runs its ragged entry point.
+FUSED_UNIT_CHANNELS = (32, 64)  # stage widths whose residual units run as one fused launch (srn_hifigan_resunit)
+
+
+def masked(lens, out=False):
+    """the length keywords of a conv whose input has `lens` rows per item (out: whose output is cut to them as well,
+    stored as 0 behind them); none for the dense plan's None"""
+    if lens is None:
+        return {}
+    return {"len_in": lens, "len_out": lens} if out else {"len_in": lens}
+
+
+def upsample_ops(ol, B, src, csrc, tsrc, up, out, slope, emb=None, len_in=None):
+    """the transposed conv of one stage, LeakyReLU in front: one conv per output phase (2 taps each) from `src`
+    (B, tsrc, csrc) into `out` (B, tsrc * s, cout).  up: the packed entry (phases, b, s, cout); emb: a residual
+    (B, tsrc * s, cout) added to the result; len_in: the lengths of the stage below, which a phase reads."""
+    s, co = up["s"], up["cout"]
+    res = {} if emb is None else dict(res=emb, res_mode=ops.RES_ADD, res_bs=tsrc * s * co, ld_res=co)
+    for r, (taps, wp) in enumerate(up["phases"]):
+        ol.append(conv_op(B, src, csrc, tsrc, wp, up["b"], out, co, tsrc, taps, pro_act=ops.ACT_LEAKY, pro_slope=slope,
+                          out_bs=tsrc * s * co, out_t_stride=s, out_t_off=r, **res, **masked(len_in)))
+
+
+def mrf_stage_ops(ol, B, u, p0, p1, xt, acc, blocks, C, T, slope, lens=None):
+    """one multi-receptive-field stage: acc = mean over `blocks` of block(u), all (B, T, C).  blocks: per block its
+    packed convs (k, d, w1, b1 and, for the two-conv unit, w2, b2); p0 / p1 ping-pong between a block's units, xt holds
+    the middle of an unfused two-conv unit; lens: the stage's lengths."""
+    nb = len(blocks)
+    for j, convs in enumerate(blocks):
+        x = u
+        for idx, cv in enumerate(convs):
+            last = idx == len(convs) - 1
+            dst = acc if last else (p0, p1)[idx % 2]
+            fin = {}
+            if last:
+                # cs += block(c); c = cs / num_blocks  (hifigan.py:183-186), in the reference's order
+                if j > 0:
+                    fin.update(res2=acc, res2_bs=T * C, ld_res2=C)
+                if j == nb - 1:
+                    fin.update(post=ops.POST_DIV, post_div=float(nb))
+            skip = dict(res=x, res_mode=ops.RES_ADD, res_bs=T * C, ld_res=C, **fin, **masked(lens))
+            if "w2" in cv and C in FUSED_UNIT_CHANNELS and (cv["k"] - 1) * cv["d"] <= 50 and cv["k"] % 2 == 1:
+                # thin stage: the whole unit in one launch (resunit.hip); stage sum / mean in its epilogue
+                ol.append(ops.ResUnitOp(x=x, w1=cv["w1"], b1=cv["b1"], w2=cv["w2"], b2=cv["b2"], out=dst, n_batch=B,
+                                        T=T, C=C, k=cv["k"], dilation=cv["d"], slope=slope, res2=fin.get("res2"),
+                                        post_div=fin.get("post_div", 0.0), lens=lens))
+            elif "w2" in cv:
+                # the second LeakyReLU (residual_block.py:252) has one consumer: it runs once per element in
+                # conv1's epilogue, not once per element per 32-deep step per column tile in conv2's loop (on
+                # the fp32 matrix pipe every vector instruction of the loop is taken from the MFMA stream)
+                ol.append(conv_op(B, x, C, T, cv["w1"], cv["b1"], xt, C, T, ops.conv_taps(cv["k"], cv["d"]),
+                                  pro_act=ops.ACT_LEAKY, pro_slope=slope, post=ops.POST_LEAKY, post_div=slope,
+                                  **masked(lens)))
+                ol.append(conv_op(B, xt, C, T, cv["w2"], cv["b2"], dst, C, T, ops.conv_taps(cv["k"], 1), **skip))
+            else:
+                ol.append(conv_op(B, x, C, T, cv["w1"], cv["b1"], dst, C, T, ops.conv_taps(cv["k"], cv["d"]),
+                                  pro_act=ops.ACT_LEAKY, pro_slope=slope, **skip))
+            x = dst
+
+
+class LengthTable:
+    """the lengths of a ragged generator plan at every rate: `scales` the cumulative up-sampling factors (1 for the
+    input frames, then one per stage), `lens` ONE (n_rates, B) int32 device tensor, `rows` its (B,) rows, which the ops
+    read when they run.  set_lengths() rewrites the tensor in place -- outside the captured graph, whose nodes only
+    carry its address."""
+
+    def __init__(self, upsample_scales, B, dev):
+        self.scales = [1]
+        for s in upsample_scales:
+            self.scales.append(self.scales[-1] * s)
+        self.lens = torch.zeros(len(self.scales), B, dtype=torch.int32, device=dev)
+        self.rows = list(self.lens.unbind(0))
+
+    def set_lengths(self, lengths):
+        """lengths: B frame counts in [1, T_cap] (validated by the caller, item_lengths)"""
+        host = torch.tensor([[int(n) * s for n in lengths] for s in self.scales], dtype=torch.int32)
+        self.lens.copy_(host)
 
 
 # ---------------------------------------------------------------------------------------------- self-attention

@@ -12,15 +12,15 @@ Mapping to kernels: every Conv1d / ConvTranspose1d phase / 1x1 conv is `srn_conv
 dilated conv gathers [x | x(t - r) | x(t + r)] rows with `srn_pd_gather` and multiplies them by [Wc | Wp | Wf] in ONE
 GEMM (K = 3C); the strided down-sampling convs use in_stride; LeakyReLUs ride in GEMM prologues / epilogues.
 """
-import functools
 from collections import OrderedDict
 
 import torch
 
 from . import _shapes, ops, vocoder
-from .models import _Packed, _fold_wn
-from .ops import ACT_LEAKY, POST_DIV, POST_LEAKY, RES_ADD
-from .plan import conv_op, dev_f32, item_lengths, lru_get, require_cuda as _require_cuda, rup
+from .models import _fold_wn
+from .ops import ACT_LEAKY, POST_LEAKY, RES_ADD
+from .plan import (LengthTable, conv_op, dev_f32, item_lengths, masked, mrf_stage_ops, require_cuda as _require_cuda,
+                   rup, upsample_ops)
 
 DEFAULT_PARAMS = dict(
     in_channels=43, out_channels=1, channels=512, kernel_size=7, upsample_scales=(5, 4, 3, 2),
@@ -67,7 +67,7 @@ def sifigan_shapes(in_channels=43, out_channels=1, channels=512, kernel_size=7, 
     return d
 
 
-class SiFiGANGenerator(_Packed):
+class SiFiGANGenerator(vocoder._Generator):
     def __init__(self, **params):
         cfg = dict(DEFAULT_PARAMS)
         cfg.update(params)
@@ -82,19 +82,6 @@ class SiFiGANGenerator(_Packed):
         self.hop = 1
         for s in cfg["upsample_scales"]:
             self.hop *= s
-
-    def remove_weight_norm(self):
-        def walk(m):
-            if "weight_g" in m._parameters:
-                g, v = m._parameters["weight_g"], m._parameters["weight_v"]
-                w = (v * (g / v.reshape(v.shape[0], -1).norm(dim=1).reshape(g.shape))).detach()
-                del m._parameters["weight_g"], m._parameters["weight_v"]
-                m.register_parameter("weight", torch.nn.Parameter(w, requires_grad=False))
-            for c in m.children():
-                walk(c)
-
-        walk(self)
-        self._invalidate()
 
     def packed(self):
         if self._packed is not None:
@@ -142,9 +129,10 @@ class SiFiGANGenerator(_Packed):
         for i in range(n):
             for j in range(nb):
                 k = fp["resblock_kernel_sizes"][j]
-                P["fn_blocks"].append([dict(k=k, d=dl, w=ops.pack_conv_weight(
+                # (HiFi-GAN's keys for a single-conv unit: plan.mrf_stage_ops reads both generators' blocks)
+                P["fn_blocks"].append([dict(k=k, d=dl, w1=ops.pack_conv_weight(
                     _fold_wn(sd, f"fn.blocks.{i * nb + j}.convs1.{idx}.1")),
-                    b=sd[f"fn.blocks.{i * nb + j}.convs1.{idx}.1.bias"])
+                    b1=sd[f"fn.blocks.{i * nb + j}.convs1.{idx}.1.bias"])
                     for idx, dl in enumerate(fp["resblock_dilations"][j])])
         P["sn_out_w"] = ops.pack_conv_weight(_fold_wn(sd, "sn.output_conv"))
         P["sn_out_b"] = sd["sn.output_conv.bias"]
@@ -164,12 +152,8 @@ class SiFiGANGenerator(_Packed):
         super()._invalidate()
         self._ragged_plans = {}  # a cache of its own: a miss in plan() clears _plans, never these
 
-    def plan_ragged(self, B, T_max, bucket=None):
-        """the ragged plan for B items of at most T_max frames: its capacity is T_max rounded up to `bucket` frames
-        (RAGGED_BUCKET), so one plan serves every batch of B whose longest item falls in the same bucket"""
-        T_cap = rup(T_max, vocoder.RAGGED_BUCKET if bucket is None else int(bucket))
-        key = (B, T_cap, ops.DEFAULT_PRECISION)
-        return lru_get(self._ragged_plans, key, 4, lambda: RaggedSiFiGANPlan(self, B, T_cap))
+    def _ragged_slot(self):
+        return self._ragged_plans, (), SiFiGANPlan
 
     @torch.no_grad()
     def forward(self, x, c, d, lengths=None):
@@ -207,34 +191,29 @@ class SiFiGANGenerator(_Packed):
         pl = self._run_ragged(len(items), max(lengths), lengths, fill)
         return [(pl.wave[b, :n * self.hop].clone(), pl.exc[b, :n * self.hop].clone()) for b, n in enumerate(lengths)]
 
-    def _run_ragged(self, B, T_max, lengths, fill):
-        """run the ragged plan of (B, T_max): `fill(plan)` writes the items into the plan's input buffers (rows past an
-        item's end keep whatever an earlier batch left there: they are never read as data); returns the plan, whose
-        wave / exc hold the result until its next run"""
-        pl = self.plan_ragged(B, T_max)
-        pl.set_lengths(lengths)
-        fill(pl)
-        pl.run()
-        return pl
-
 
 class SiFiGANPlan:
-    def __init__(self, gen, B, T):
-        self._build(gen, B, T, None)
+    """Buffers + op list of one generator forward for (B, T).  Inputs: load(); outputs: self.wave and self.exc
+    (B, T * hop).
 
-    def _build(self, gen, B, T, lens):
-        """the walk of the dense plan and of RaggedSiFiGANPlan.  lens: None, or one (B,) int32 device tensor per rate --
-        lens[0] for the analysis frames, lens[i + 1] behind upsample i, lens[-1] the final (waveform) rate -- which makes
-        every length data: each conv gets the lengths of the buffer it reads as len_in (rows at or past them read as the
-        zeros an item alone would be padded with), the gather and the output stage run their ragged entry points and the
-        excitation's conv zeroes its own tail (len_out)."""
+    ragged: the lengths are data -- one plan (and one captured graph) for every batch of B items whose longest has at
+    most T frames.  Inputs (load_item / load_batch): rows at or past an item's length may hold anything; wave and exc
+    are zero past each item's end, and item b is computed as its own B = 1 dense plan of lengths[b] frames computes it.
+    self.lens (plan.LengthTable: row 0 for the analysis frames, row i + 1 behind upsample i, the last the waveform
+    rate) holds what set_lengths() was given; every conv gets the row of the buffer it reads as len_in, the gather and
+    the output stage run their ragged entry points and the excitation's conv zeroes its own tail (len_out)."""
+
+    def __init__(self, gen, B, T, ragged=False):
         P, cfg = gen.packed(), gen.cfg
-        masked = (lambda st: {}) if lens is None else (lambda st: {"len_in": lens[st]})
         dev = gen._device()
         slope = gen.slope
         f = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
         scales = cfg["upsample_scales"]
         n = len(scales)
+        lens = [None] * (n + 1)
+        if ragged:
+            table = LengthTable(scales, B, dev)
+            self.lens, self.scales, self.set_lengths, lens = table.lens, table.scales, table.set_lengths, table.rows
         C0 = cfg["channels"]
         Rs, Cs = [], []
         r = T
@@ -255,9 +234,8 @@ class SiFiGANPlan:
         ol = [ops.transpose_op(self._c_in, c_cl, B, cin, T, cin * T, T, T * cin_p, cin_p),
               ops.copy_channels_op(self._x_in, Rf, 1, 0, x_cl, Rf * 4, 4, 0, B, Rf, 1)]
 
-        conv = functools.partial(conv_op, B)
         h = f(B, T, C0)
-        ol.append(conv(c_cl, cin_p, T, P["in_w"], P["in_b"], h, C0, T, ops.conv_taps(ks), **masked(0)))
+        ol.append(conv_op(B, c_cl, cin_p, T, P["in_w"], P["in_b"], h, C0, T, ops.conv_taps(ks), **masked(lens[0])))
 
         def down(net, first):
             """first: (B, Rf, Cl) feature at the final rate -> list of features down to the first stage's rate"""
@@ -266,118 +244,68 @@ class SiFiGANPlan:
             for j, dn in enumerate(P[net + "_down"]):  # conv j reads the rate behind upsample n - 1 - j: its lengths
                 ro = rc // dn["s"]
                 o = f(B, ro, dn["cout"])
-                ol.append(conv(cur, dn["cin"], rc, dn["w"], dn["b"], o, dn["cout"], ro, dn["taps"], in_stride=dn["s"],
-                               post=POST_LEAKY, post_div=slope, **masked(n - j)))
+                ol.append(conv_op(B, cur, dn["cin"], rc, dn["w"], dn["b"], o, dn["cout"], ro, dn["taps"],
+                                  in_stride=dn["s"], post=POST_LEAKY, post_div=slope, **masked(lens[n - j])))
                 feats.append(o)
                 cur, rc = o, ro
             return feats
 
-        def up(net, i, src, csrc, rsrc, emb, out):
-            u = P[net + "_up"][i]
-            s, co, ro = u["s"], u["cout"], rsrc * u["s"]
-            for ph, (taps, wp) in enumerate(u["phases"]):  # a phase reads the stage below: its lengths
-                ol.append(conv(src, csrc, rsrc, wp, u["b"], out, co, rsrc, taps, pro_act=ACT_LEAKY, pro_slope=slope,
-                               out_bs=ro * co, out_t_stride=s, out_t_off=ph, res=emb, res_mode=RES_ADD,
-                               res_bs=ro * co, ld_res=co, **masked(i)))
-
         # ---- source network
         emb0 = f(B, Rf, Cl)
-        ol.append(conv(x_cl, 4, Rf, P["emb_w"], P["emb_b"], emb0, Cl, Rf, ops.conv_taps(ks), **masked(n)))
+        ol.append(conv_op(B, x_cl, 4, Rf, P["emb_w"], P["emb_b"], emb0, Cl, Rf, ops.conv_taps(ks), **masked(lens[n])))
         embs = down("sn", emb0)
         e_a, e_b, g3, xt = f(B * big), f(B * big), f(B * 3 * big), f(B * big)
         cur, ccur, rcur = h, C0, T
         for i in range(n):
             C, R = Cs[i], Rs[i]
-            here = masked(i + 1)
             x_, y_ = (e_a, e_b) if cur is not e_a else (e_b, e_a)  # never up-sample a buffer onto itself
-            up("sn", i, cur, ccur, rcur, embs[-i - 1], x_)
+            upsample_ops(ol, B, cur, ccur, rcur, P["sn_up"][i], x_, slope, emb=embs[-i - 1], len_in=lens[i])
             for blk in P["sn_blocks"][i]:
-                if lens is None:
-                    ol.append(ops.pd_gather_op(x_, self.d[i], g3, B, R, C, blk["dil"], slope))
-                else:  # g3 rows past an item's end keep what they held: the GEMM behind reads them as zero
-                    ol.append(ops.pd_gather_ragged_op(x_, self.d[i], lens[i + 1], g3, B, R, C, blk["dil"], slope))
+                # ragged: g3 rows past an item's end keep what they held: the GEMM behind reads them as zero
+                ol.append(ops.pd_gather_op(x_, self.d[i], g3, B, R, C, blk["dil"], slope, lens=lens[i + 1]))
+                skip = dict(res=x_, res_mode=RES_ADD, res_bs=R * C, ld_res=C, **masked(lens[i + 1]))
                 if "wa" in blk:
-                    ol.append(conv(g3, 3 * C, R, blk["w3"], blk["b3"], xt, C, R, [0], **here))
-                    ol.append(conv(xt, C, R, blk["wa"], blk["ba"], y_, C, R, ops.conv_taps(3), pro_act=ACT_LEAKY,
-                                   pro_slope=slope, res=x_, res_mode=RES_ADD, res_bs=R * C, ld_res=C, **here))
+                    ol.append(conv_op(B, g3, 3 * C, R, blk["w3"], blk["b3"], xt, C, R, [0], **masked(lens[i + 1])))
+                    ol.append(conv_op(B, xt, C, R, blk["wa"], blk["ba"], y_, C, R, ops.conv_taps(3), pro_act=ACT_LEAKY,
+                                      pro_slope=slope, **skip))
                 else:
-                    ol.append(conv(g3, 3 * C, R, blk["w3"], blk["b3"], y_, C, R, [0], res=x_, res_mode=RES_ADD,
-                                   res_bs=R * C, ld_res=C, **here))
+                    ol.append(conv_op(B, g3, 3 * C, R, blk["w3"], blk["b3"], y_, C, R, [0], **skip))
                 x_, y_ = y_, x_
             cur, ccur, rcur = x_, C, R
         e_fin = f(B, Rf, Cl)
         ol.append(ops.copy_channels_op(cur, Rf * Cl, Cl, 0, e_fin, Rf * Cl, Cl, 0, B, Rf, Cl))
         self.exc = f(B, Rf)
         # ragged: len_out makes the conv store 0 at rows past an item's end (a select in the kernel's epilogue)
-        ol.append(conv(e_fin, Cl, Rf, P["sn_out_w"], P["sn_out_b"], self.exc, 1, Rf, ops.conv_taps(ks), **masked(n),
-                       **({} if lens is None else {"len_out": lens[n]})))
+        ol.append(conv_op(B, e_fin, Cl, Rf, P["sn_out_w"], P["sn_out_b"], self.exc, 1, Rf, ops.conv_taps(ks),
+                          **masked(lens[n], out=True)))
         # ---- filter network
         fembs = down("fn", e_fin)
         u_, p0, p1, acc = f(B * big), f(B * big), f(B * big), f(B * big)
-        fp = cfg["filter_network_params"]
-        nb = len(fp["resblock_kernel_sizes"])
+        nb = len(cfg["filter_network_params"]["resblock_kernel_sizes"])
         cur, ccur, rcur = h, C0, T
         for i in range(n):
-            C, R = Cs[i], Rs[i]
-            here = masked(i + 1)
-            up("fn", i, cur, ccur, rcur, fembs[-i - 1], u_)
-            for j in range(nb):
-                convs = P["fn_blocks"][i * nb + j]
-                x_ = u_
-                pp = [p0, p1]
-                for idx, cv in enumerate(convs):
-                    last = idx == len(convs) - 1
-                    dst = acc if last else pp[idx % 2]
-                    fin = {}
-                    if last:
-                        if j > 0:
-                            fin.update(res2=acc, res2_bs=R * C, ld_res2=C)
-                        if j == nb - 1:
-                            fin.update(post=POST_DIV, post_div=float(nb))
-                    ol.append(conv(x_, C, R, cv["w"], cv["b"], dst, C, R, ops.conv_taps(cv["k"], cv["d"]),
-                                   pro_act=ACT_LEAKY, pro_slope=slope, res=x_, res_mode=RES_ADD, res_bs=R * C,
-                                   ld_res=C, **fin, **here))
-                    x_ = dst
-            cur, ccur, rcur = acc, C, R
+            upsample_ops(ol, B, cur, ccur, rcur, P["fn_up"][i], u_, slope, emb=fembs[-i - 1], len_in=lens[i])
+            mrf_stage_ops(ol, B, u_, p0, p1, xt, acc, P["fn_blocks"][i * nb:(i + 1) * nb], Cs[i], Rs[i], slope,
+                          lens[i + 1])
+            cur, ccur, rcur = acc, Cs[i], Rs[i]
         self.wave = f(B, Rf)
-        if lens is None:
-            ol.append(ops.out_conv_tanh_op(cur, P["fn_out_w"], P["fn_out_b"], self.wave, B, Rf, Cl, ks, slope))
-        else:
-            ol.append(ops.out_conv_tanh_ragged_op(cur, P["fn_out_w"], P["fn_out_b"], self.wave, lens[n], B, Rf, Cl, ks,
-                                                  slope))
+        ol.append(ops.out_conv_tanh_op(cur, P["fn_out_w"], P["fn_out_b"], self.wave, B, Rf, Cl, ks, slope,
+                                       lens=lens[n]))
         self.ops = ol
+        # the dense plan runs its ops one by one; a ragged plan goes through the runner, like every other plan
+        self._runner = ops.GraphRunner(lambda: self.ops) if ragged else None
+
+    def run(self):
+        if self._runner is not None:
+            return self._runner()
+        for op in self.ops:
+            op()
 
     def load(self, x, c, d):
         self._c_in.copy_(c)
         self._x_in.copy_(x.reshape(self.B, -1))
         for buf, di in zip(self.d, d):
             buf.copy_(di.reshape(self.B, -1))
-
-    def run(self):
-        for op in self.ops:
-            op()
-
-
-class RaggedSiFiGANPlan(SiFiGANPlan):
-    """SiFiGANPlan with the lengths as data: one plan (and one captured graph) for every batch of B items whose longest
-    has at most T_cap frames.  Inputs (load_item / load_batch): rows at or past an item's length may hold anything;
-    outputs: self.wave and self.exc (B, T_cap * hop), zero past each item's end.  Item b is computed as its own B = 1
-    dense plan of lengths[b] frames computes it.  self.lens (n_stages + 1, B) int32 holds the per-rate lengths the ops
-    read when they run: set_lengths() rewrites it in place -- outside the captured graph, whose nodes only carry its
-    address."""
-
-    def __init__(self, gen, B, T_cap):
-        self.scales = [1]
-        for s in gen.cfg["upsample_scales"]:
-            self.scales.append(self.scales[-1] * s)
-        self.lens = torch.zeros(len(self.scales), B, dtype=torch.int32, device=gen._device())
-        self._build(gen, B, T_cap, list(self.lens.unbind(0)))
-        self._runner = ops.GraphRunner(lambda: self.ops)
-
-    def set_lengths(self, lengths):
-        """lengths: B frame counts in [1, T_cap] (validated by the caller, plan.item_lengths)"""
-        host = torch.tensor([[int(n) * s for n in lengths] for s in self.scales], dtype=torch.int32)
-        self.lens.copy_(host)
 
     def load_item(self, b, x, c, d):
         """item b: x (..., T_b * hop), c (in_ch, T_b) or (1, in_ch, T_b), d[i] (..., T_b * cumprod(scales)[i]) into the
@@ -391,7 +319,7 @@ class RaggedSiFiGANPlan(SiFiGANPlan):
             buf[b, :di.numel()].copy_(di)
 
     def load_batch(self, x, c, d):
-        """the (B, ., T) tensors of a forward(lengths=) call, T <= T_cap, into the front of every item's rows"""
+        """the (B, ., T) tensors of a forward(lengths=) call, T <= the plan's, into the front of every item's rows"""
         T = c.shape[2]
         self._c_in[:, :, :T].copy_(c)
         x = x.reshape(self.B, -1)
@@ -399,6 +327,3 @@ class RaggedSiFiGANPlan(SiFiGANPlan):
         for buf, di in zip(self.d, d):
             di = di.reshape(self.B, -1)
             buf[:, :di.shape[1]].copy_(di)
-
-    def run(self):
-        self._runner()

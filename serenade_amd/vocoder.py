@@ -11,7 +11,6 @@ Everything is computed channels-last by libserenade_hip.so: the transposed convo
 implicit-GEMM launch per output phase (2 taps each), every residual-stack conv has the LeakyReLU
 fused into its input gather and bias / residual / stage-mean fused into its epilogue.
 """
-import functools
 import logging
 import os
 import time
@@ -21,8 +20,9 @@ import yaml
 
 from . import _shapes, ops
 from .models import _Packed, _fold_wn
-from .ops import ACT_LEAKY, POST_DIV, POST_LEAKY, RES_ADD
-from .plan import conv_op, dev_f32, item_lengths, lru_get, require_cuda as _require_cuda, rup
+from .plan import FUSED_UNIT_CHANNELS  # noqa: F401  (its public name is vocoder.FUSED_UNIT_CHANNELS)
+from .plan import (LengthTable, conv_op, dev_f32, item_lengths, lru_get, masked, mrf_stage_ops,
+                   require_cuda as _require_cuda, rup, upsample_ops)
 
 __all__ = ["HiFiGANGenerator", "Vocoder", "load_vocoder", "hifigan_state_shapes"]
 
@@ -31,7 +31,48 @@ def hifigan_state_shapes(**params):
     return _shapes.as_meta(_shapes.hifigan_shapes(**params))
 
 
-class HiFiGANGenerator(_Packed):
+RAGGED_BUCKET = 64  # frames: a ragged plan's capacity is the batch maximum rounded up to this
+
+
+class _Generator(_Packed):
+    """what HiFiGANGenerator and SiFiGANGenerator share: the weight-norm fold and how a ragged plan is found and run.
+    A generator says where its ragged plans are cached and what makes one (_ragged_slot: cache, key tag, plan class)."""
+
+    def remove_weight_norm(self):
+        """hifigan.py:206-217: replace (weight_g, weight_v) by the folded weight."""
+
+        def walk(m):
+            if "weight_g" in m._parameters:
+                g, v = m._parameters["weight_g"], m._parameters["weight_v"]
+                norm = v.reshape(v.shape[0], -1).norm(dim=1).reshape(g.shape)
+                w = (v * (g / norm)).detach()
+                del m._parameters["weight_g"], m._parameters["weight_v"]
+                m.register_parameter("weight", torch.nn.Parameter(w, requires_grad=False))
+            for c in m.children():
+                walk(c)
+
+        walk(self)
+        self._invalidate()
+
+    def plan_ragged(self, B, T_max, bucket=None):
+        """the ragged plan for B items of at most T_max frames: its capacity is T_max rounded up to `bucket` frames
+        (RAGGED_BUCKET), so one plan serves every batch of B whose longest item falls in the same bucket"""
+        T_cap = rup(T_max, RAGGED_BUCKET if bucket is None else int(bucket))
+        cache, tag, make = self._ragged_slot()
+        return lru_get(cache, tag + (B, T_cap, ops.DEFAULT_PRECISION), 4, lambda: make(self, B, T_cap, ragged=True))
+
+    def _run_ragged(self, B, T_max, lengths, fill):
+        """run the ragged plan of (B, T_max): `fill(plan)` writes the items into the plan's input buffers (rows past an
+        item's end keep whatever an earlier batch left there: they are never read as data); returns the plan, whose
+        outputs hold the result until its next run"""
+        pl = self.plan_ragged(B, T_max)
+        pl.set_lengths(lengths)
+        fill(pl)
+        pl.run()
+        return pl
+
+
+class HiFiGANGenerator(_Generator):
     def __init__(self, in_channels=80, out_channels=1, channels=512, kernel_size=7, upsample_scales=(8, 8, 2, 2),
                  upsample_kernel_sizes=(16, 16, 4, 4), resblock_kernel_sizes=(3, 7, 11),
                  resblock_dilations=[(1, 3, 5), (1, 3, 5), (1, 3, 5)], use_additional_convs=True, bias=True,
@@ -62,22 +103,6 @@ class HiFiGANGenerator(_Packed):
             self.hop *= s
 
     # ------------------------------------------------------------------ reference API
-    def remove_weight_norm(self):
-        """hifigan.py:206-217: replace (weight_g, weight_v) by the folded weight."""
-
-        def walk(m):
-            if "weight_g" in m._parameters:
-                g, v = m._parameters["weight_g"], m._parameters["weight_v"]
-                norm = v.reshape(v.shape[0], -1).norm(dim=1).reshape(g.shape)
-                w = (v * (g / norm)).detach()
-                del m._parameters["weight_g"], m._parameters["weight_v"]
-                m.register_parameter("weight", torch.nn.Parameter(w, requires_grad=False))
-            for c in m.children():
-                walk(c)
-
-        walk(self)
-        self._invalidate()
-
     def apply_weight_norm(self):
         raise NotImplementedError("training-only (hifigan.py:219-230)")
 
@@ -126,12 +151,8 @@ class HiFiGANGenerator(_Packed):
         key = (B, T, ops.DEFAULT_PRECISION)
         return lru_get(self._plans, key, 4, lambda: HiFiGANPlan(self, B, T))
 
-    def plan_ragged(self, B, T_max, bucket=None):
-        """the ragged plan for B items of at most T_max frames: its capacity is T_max rounded up to `bucket` frames
-        (RAGGED_BUCKET), so one plan serves every batch of B whose longest item falls in the same bucket"""
-        T_cap = rup(T_max, RAGGED_BUCKET if bucket is None else int(bucket))
-        key = ("ragged", B, T_cap, ops.DEFAULT_PRECISION)
-        return lru_get(self._plans, key, 4, lambda: RaggedHiFiGANPlan(self, B, T_cap))
+    def _ragged_slot(self):
+        return self._plans, ("ragged",), HiFiGANPlan  # the dense plans' LRU, the key tagged
 
     @torch.no_grad()
     def forward(self, c):
@@ -195,135 +216,54 @@ class HiFiGANGenerator(_Packed):
         pl = self._run_ragged(len(cs), max(lengths), lengths, fill)
         return [pl.wave[b, :n * self.hop].clone() for b, n in enumerate(lengths)]
 
-    def _run_ragged(self, B, T_max, lengths, fill):
-        """run the ragged plan of (B, T_max): `fill(plan)` writes the items into plan.c_in (rows past an item's end keep
-        whatever an earlier batch left there: they are never read as data); returns the plan, whose wave holds the
-        result until its next run"""
-        pl = self.plan_ragged(B, T_max)
-        pl.set_lengths(lengths)
-        fill(pl)
-        pl.run()
-        return pl
-
-
-FUSED_UNIT_CHANNELS = (32, 64)  # stage widths whose residual units run as one fused launch (srn_hifigan_resunit)
-
 
 class HiFiGANPlan:
     """Buffers + op list of one generator forward for (B, T).  Input: self.c_in (B, T, in_ch) channels-last;
-    output: self.wave (B, T * hop)."""
+    output: self.wave (B, T * hop).
 
-    def __init__(self, gen, B, T):
-        self._build(gen, B, T, None)
+    ragged: the lengths are data -- one plan (and one captured graph) for every batch of B items whose longest has at
+    most T frames.  Rows of c_in at or past an item's length may hold anything, wave is zero past each item's end, and
+    item b is computed as its own B = 1 dense plan of lengths[b] frames computes it.  self.lens (plan.LengthTable: row 0
+    for the mel frames, row i + 1 behind upsample i) holds what set_lengths() was given; every conv gets its input
+    stage's row as len_in, the fused units and the output stage run their ragged entry points."""
 
-    def _build(self, gen, B, T, lens):
-        """the stage walk of the dense plan and of RaggedHiFiGANPlan.  lens: None, or one (B,) int32 device tensor per
-        stage -- lens[0] for the mel frames, lens[i + 1] behind upsample i -- which makes every length data: each conv
-        gets its input stage's lengths as len_in (rows at or past them read as the zeros an item alone would be padded
-        with), the fused units and the output stage run their ragged entry points."""
+    def __init__(self, gen, B, T, ragged=False):
         P = gen.packed()
         dev = gen._device()
         self.B, self.T = B, T
+        lens = [None] * (len(P["ups"]) + 1)
+        if ragged:
+            table = LengthTable(gen.upsample_scales, B, dev)
+            self.lens, self.scales, self.set_lengths, lens = table.lens, table.scales, table.set_lengths, table.rows
+        self.c_raw = None  # Vocoder's ragged batch in front of the renormalisation: allocated when first used
         f = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
         self.c_in = f(B, T, gen.in_channels)
         C0 = gen.channels
         h = f(B, T, C0)
         # widest (T_i * C_i) stage decides the ping-pong buffer size
-        Ts, Cs = [], []
-        t, c = T, C0
+        big, t = 0, T
         for up in P["ups"]:
-            t, c = t * up["s"], up["cout"]
-            Ts.append(t)
-            Cs.append(c)
-        big = max(a * b for a, b in zip(Ts, Cs))
+            t *= up["s"]
+            big = max(big, t * up["cout"])
         u, p0, p1, xt, acc = (f(B * big) for _ in range(5))
-        self.wave = f(B, Ts[-1])
-        slope = gen.slope
-        ol = []
-
-        masked = (lambda st: {}) if lens is None else (lambda st: {"len_in": lens[st]})
-        conv = functools.partial(conv_op, B)
-        ol.append(conv(self.c_in, gen.in_channels, T, P["in_w"], P["in_b"], h, C0, T, ops.conv_taps(gen.kernel_size),
-                       **masked(0)))
-        cur, ccur, tcur = h, C0, T
+        self.wave = f(B, t)
         nb = gen.num_blocks
+        ol = [conv_op(B, self.c_in, gen.in_channels, T, P["in_w"], P["in_b"], h, C0, T, ops.conv_taps(gen.kernel_size),
+                      **masked(lens[0]))]
+        cur, ccur, tcur = h, C0, T
         for i, up in enumerate(P["ups"]):
-            s, C, Tn = up["s"], up["cout"], Ts[i]
-            for r, (taps, wp) in enumerate(up["phases"]):  # a phase reads the stage below: its lengths
-                ol.append(conv(cur, ccur, tcur, wp, up["b"], u, C, tcur, taps, pro_act=ACT_LEAKY, pro_slope=slope,
-                               out_bs=Tn * C, out_t_stride=s, out_t_off=r, **masked(i)))
-            here = masked(i + 1)
-            for j in range(nb):
-                convs = P["blocks"][i * nb + j]
-                x = u
-                pp = [p0, p1]
-                for idx, cv in enumerate(convs):
-                    last = idx == len(convs) - 1
-                    dst = acc if last else pp[idx % 2]
-                    fin = {}
-                    if last:
-                        # cs += block(c); c = cs / num_blocks  (hifigan.py:183-186), in the reference's order
-                        if j > 0:
-                            fin.update(res2=acc, res2_bs=Tn * C, ld_res2=C)
-                        if j == nb - 1:
-                            fin.update(post=POST_DIV, post_div=float(nb))
-                    if "w2" in cv and C in FUSED_UNIT_CHANNELS and (cv["k"] - 1) * cv["d"] <= 50 and cv["k"] % 2 == 1:
-                        # thin stage: the whole unit in one launch (resunit.hip); stage sum / mean in its epilogue
-                        unit = dict(x=x, w1=cv["w1"], b1=cv["b1"], w2=cv["w2"], b2=cv["b2"], out=dst, n_batch=B, T=Tn,
-                                    C=C, k=cv["k"], dilation=cv["d"], slope=slope, res2=fin.get("res2"),
-                                    post_div=fin.get("post_div", 0.0))
-                        ol.append(ops.ResUnitOp(**unit) if lens is None
-                                  else ops.RaggedResUnitOp(lens=lens[i + 1], **unit))
-                    elif "w2" in cv:
-                        # the second LeakyReLU (residual_block.py:252) has one consumer: it runs once per element in
-                        # conv1's epilogue, not once per element per 32-deep step per column tile in conv2's loop (on
-                        # the fp32 matrix pipe every vector instruction of the loop is taken from the MFMA stream)
-                        ol.append(conv(x, C, Tn, cv["w1"], cv["b1"], xt, C, Tn, ops.conv_taps(cv["k"], cv["d"]),
-                                       pro_act=ACT_LEAKY, pro_slope=slope, post=POST_LEAKY, post_div=slope, **here))
-                        ol.append(conv(xt, C, Tn, cv["w2"], cv["b2"], dst, C, Tn, ops.conv_taps(cv["k"], 1),
-                                       res=x, res_mode=RES_ADD, res_bs=Tn * C, ld_res=C, **fin, **here))
-                    else:
-                        ol.append(conv(x, C, Tn, cv["w1"], cv["b1"], dst, C, Tn, ops.conv_taps(cv["k"], cv["d"]),
-                                       pro_act=ACT_LEAKY, pro_slope=slope, res=x, res_mode=RES_ADD, res_bs=Tn * C,
-                                       ld_res=C, **fin, **here))
-                    x = dst
-            cur, ccur, tcur = acc, C, Tn
-            # the next stage's upsample reads `acc` and writes `u`; resblocks then overwrite acc only at their end
-        if lens is None:
-            ol.append(ops.out_conv_tanh_op(cur, P["out_w"], P["out_b"], self.wave, B, tcur, ccur, gen.kernel_size, 0.01))
-        else:
-            ol.append(ops.out_conv_tanh_ragged_op(cur, P["out_w"], P["out_b"], self.wave, lens[-1], B, tcur, ccur,
-                                                  gen.kernel_size, 0.01))
+            # the upsample reads `cur` (h, then acc) and writes `u`; the blocks overwrite acc only at their end
+            upsample_ops(ol, B, cur, ccur, tcur, up, u, gen.slope, len_in=lens[i])
+            cur, ccur, tcur = acc, up["cout"], tcur * up["s"]
+            mrf_stage_ops(ol, B, u, p0, p1, xt, acc, P["blocks"][i * nb:(i + 1) * nb], ccur, tcur, gen.slope,
+                          lens[i + 1])
+        ol.append(ops.out_conv_tanh_op(cur, P["out_w"], P["out_b"], self.wave, B, tcur, ccur, gen.kernel_size, 0.01,
+                                       lens=lens[-1]))
         self.ops = ol
         self._runner = ops.GraphRunner(lambda: self.ops)
 
     def run(self):
         self._runner()
-
-
-RAGGED_BUCKET = 64  # frames: a ragged plan's capacity is the batch maximum rounded up to this (DESIGN.md section 7i)
-
-
-class RaggedHiFiGANPlan(HiFiGANPlan):
-    """HiFiGANPlan with the lengths as data: one plan (and one captured graph) for every batch of B items whose longest
-    has at most T_cap frames.  Input: self.c_in (B, T_cap, in_ch), rows at or past an item's length may hold anything;
-    output: self.wave (B, T_cap * hop), zero past each item's end.  Item b is computed as its own B = 1 dense plan of
-    lengths[b] frames computes it.  self.lens (n_stages + 1, B) int32 holds the per-stage lengths the ops read when they
-    run: set_lengths() rewrites it in place -- outside the captured graph, whose nodes only carry its address."""
-
-    def __init__(self, gen, B, T_cap):
-        dev = gen._device()
-        self.scales = [1]
-        for s in gen.upsample_scales:
-            self.scales.append(self.scales[-1] * s)
-        self.lens = torch.zeros(len(self.scales), B, dtype=torch.int32, device=dev)
-        self.c_raw = None  # Vocoder: the padded batch in front of the renormalisation
-        self._build(gen, B, T_cap, list(self.lens.unbind(0)))
-
-    def set_lengths(self, lengths):
-        """lengths: B frame counts in [1, T_cap] (validated by the caller, plan.item_lengths)"""
-        host = torch.tensor([[int(n) * s for n in lengths] for s in self.scales], dtype=torch.int32)
-        self.lens.copy_(host)
 
 
 def load_vocoder(checkpoint, config=None, stats=None):
@@ -382,13 +322,16 @@ class Vocoder(object):
     def _decode_cl(self, c):
         """c (B, T, 80) normalised mel -> (B, T * hop): both affine maps and the generator on the GPU."""
         _require_cuda(c, "Vocoder.decode")
-        B, T, C = c.shape
-        pl = self.model.plan(B, T)
-        ts = self.trg_stats if self.take_norm_feat else {"scale": None, "mean": None}
-        ops.renorm_op(c.detach().to(torch.float32).contiguous(), ts["scale"], ts["mean"], self.stats["mean"],
-                      self.stats["scale"], pl.c_in, B * T, C)()
-        pl.run()
+        pl = self.model.plan(c.shape[0], c.shape[1])
+        self._renorm_run(c.detach().to(torch.float32).contiguous(), pl)
         return pl.wave.clone()
+
+    def _renorm_run(self, c, pl):
+        """c (B, T, 80) -> pl.c_in in ONE srn_renorm, then the plan"""
+        B, T, C = c.shape
+        ts = self.trg_stats if self.take_norm_feat else {"scale": None, "mean": None}
+        ops.renorm_op(c, ts["scale"], ts["mean"], self.stats["mean"], self.stats["scale"], pl.c_in, B * T, C)()
+        pl.run()
 
     @torch.no_grad()
     def decode(self, c):
@@ -430,15 +373,12 @@ class Vocoder(object):
         return [pl.wave[b, :n * self.model.hop].clone() for b, n in enumerate(lengths)]
 
     def _decode_ragged(self, B, T_max, lengths, fill):
-        """the padded batch goes through ONE srn_renorm (all T_cap rows of every item: the rows past an item's end are
-        renormalised leftovers, never read as data), then through the ragged plan"""
+        """the padded batch goes through the one srn_renorm (all T_cap rows of every item: the rows past an item's end
+        are renormalised leftovers, never read as data), then through the ragged plan"""
         pl = self.model.plan_ragged(B, T_max)
         if pl.c_raw is None:
             pl.c_raw = torch.zeros_like(pl.c_in)
         pl.set_lengths(lengths)
         fill(pl.c_raw)
-        ts = self.trg_stats if self.take_norm_feat else {"scale": None, "mean": None}
-        ops.renorm_op(pl.c_raw, ts["scale"], ts["mean"], self.stats["mean"], self.stats["scale"], pl.c_in,
-                      pl.c_raw.shape[0] * pl.c_raw.shape[1], pl.c_raw.shape[2])()
-        pl.run()
+        self._renorm_run(pl.c_raw, pl)
         return pl

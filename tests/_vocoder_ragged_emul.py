@@ -63,9 +63,12 @@ class installed(_emulator.installed):
             else:
                 base_call(self_, stream)
         ops.CallOp.__call__ = call
-        ops.RaggedResUnitOp.__call__ = lambda self_, stream=None: emul_resunit_ragged(self_.kw)
-        return self
+        base_unit = ops.ResUnitOp.__call__  # the emulator's
 
-    def __exit__(self, *exc):
-        del ops.RaggedResUnitOp.__call__  # back to _StructOp's
-        super().__exit__(*exc)  # restores CallOp.__call__ as it was before both layers
+        def unit(self_, stream=None):
+            if self_.name == "srn_hifigan_resunit_ragged":
+                emul_resunit_ragged(self_.kw)
+            else:
+                base_unit(self_, stream)
+        ops.ResUnitOp.__call__ = unit
+        return self  # (_emulator.installed.__exit__ restores both __call__s as they were before both layers)

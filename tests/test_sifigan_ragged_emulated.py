@@ -1,5 +1,5 @@
 """The ragged SiFiGAN's host logic on the CPU, through the C-ABI emulator plus the executable specification of the ragged
-gather (tests/_sifigan_ragged_emul.py): RaggedSiFiGANPlan (per-rate lengths, len_in on every conv, bucketed capacity,
+gather (tests/_sifigan_ragged_emul.py): the ragged SiFiGANPlan (per-rate lengths, len_in on every conv, bucketed capacity,
 plan reuse, a cache the dense plan() leaves alone), `forward(lengths=)` / `inference_ragged`, and the CLI option.
 The kernel itself is tests/test_zz_hip_sifigan_ragged.py (GPU)."""
 import numpy as np
@@ -112,17 +112,15 @@ def test_batch_utterances_below_one_is_rejected():
 
 
 def test_dense_plan_is_op_for_op_what_build_without_lengths_gives():
-    """SiFiGANPlan is _build(..., None): the op names and their count are the dense plan's own, and the ragged walk
-    differs from it only in the gather, the output stage and the lengths it hands to the same convs"""
+    """one walk builds both plans: the ragged one differs from the dense one only in the gather, the output stage and
+    the lengths it hands to the same convs (tests/test_vocoder_oplists_emulated.py holds both to their recorded op
+    lists)"""
     g, w = _model(SMALL)
     with _emulator.installed():
         dense = sifigan.SiFiGANPlan(g, 2, 11)
-        again = sifigan.SiFiGANPlan.__new__(sifigan.SiFiGANPlan)
-        again._build(g, 2, 11, None)
-        ragged = sifigan.RaggedSiFiGANPlan(g, 2, 11)
+        ragged = sifigan.SiFiGANPlan(g, 2, 11, ragged=True)
     name = lambda op: getattr(op, "name", type(op).__name__)
     names = [name(op) for op in dense.ops]
-    assert [name(op) for op in again.ops] == names and len(again.ops) == len(dense.ops)
     assert "srn_pd_gather" in names and "srn_out_conv_tanh" in names and not any("ragged" in n for n in names)
     swap = {"srn_pd_gather": "srn_pd_gather_ragged", "srn_out_conv_tanh": "srn_out_conv_tanh_ragged"}
     assert [name(op) for op in ragged.ops] == [swap.get(n, n) for n in names]

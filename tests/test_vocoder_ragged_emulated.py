@@ -1,7 +1,7 @@
 """The ragged vocoder's host logic on the CPU, through the C-ABI emulator plus the executable specifications of the two
-ragged entry points (tests/_vocoder_ragged_emul.py): RaggedHiFiGANPlan (per-stage lengths, len_in on every conv, bucketed
-capacity, plan reuse), the public additions of HiFiGANGenerator / Vocoder, and `serenade-decode --ragged-vocoder`.
-The kernels themselves are tests/test_zz_hip_vocoder_ragged.py (GPU)."""
+ragged entry points (tests/_vocoder_ragged_emul.py): the ragged HiFiGANPlan (per-stage lengths, len_in on every conv,
+bucketed capacity, plan reuse), the public additions of HiFiGANGenerator / Vocoder, and `serenade-decode
+--ragged-vocoder`.  The kernels themselves are tests/test_zz_hip_vocoder_ragged.py (GPU)."""
 import os
 import wave as wavmod
 
@@ -104,10 +104,14 @@ def test_vocoder_decode_ragged_equals_decode(monkeypatch):
 
 
 def _count_ragged_ops(monkeypatch):
+    """the entry names ending in _ragged of every op built from here on"""
     built = []
-    unit_init, out_op = ops.RaggedResUnitOp.__init__, ops.out_conv_tanh_ragged_op
-    monkeypatch.setattr(ops.RaggedResUnitOp, "__init__", lambda self_, **kw: (built.append("unit"), unit_init(self_, **kw))[1])
-    monkeypatch.setattr(ops, "out_conv_tanh_ragged_op", lambda *a: (built.append("out"), out_op(*a))[1])
+    for cls in (ops._StructOp, ops.CallOp):  # both take the entry name first
+        def init(self_, name, args, _init=cls.__init__):
+            if name.endswith("_ragged"):
+                built.append(name)
+            _init(self_, name, args)
+        monkeypatch.setattr(cls, "__init__", init)
     return built
 
 
@@ -127,7 +131,7 @@ def test_cli_ragged_vocoder_writes_what_the_loop_writes(tmp_path, monkeypatch):
                 assert not built, "without --ragged-vocoder nothing builds a ragged op"
         with pytest.raises(SystemExit):
             ssc_decode.main(argv + ["--outdir", str(tmp_path / "bad"), "--ragged-vocoder"])
-    assert "unit" in built and "out" in built
+    assert "srn_hifigan_resunit_ragged" in built and "srn_out_conv_tanh_ragged" in built
     assert outs["loop"] == outs["ragged"] and len(outs["loop"]) == 12
     for f in outs["loop"]:
         a, b = tmp_path / "loop" / f, tmp_path / "ragged" / f

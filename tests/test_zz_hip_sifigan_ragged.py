@@ -87,7 +87,7 @@ def check_gather(dev, B, T, C, dil, lens):
     lens_dev = torch.tensor(lens, dtype=torch.int32, device=dev)
     buf = sentinel(2 * GUARD + B * T * 3 * C, dev)
     out = buf[GUARD:GUARD + B * T * 3 * C].view(B, T, 3 * C)
-    ops.pd_gather_ragged_op(x, d, lens_dev, (buf, GUARD), B, T, C, dil, SLOPE)()
+    ops.pd_gather_op(x, d, (buf, GUARD), B, T, C, dil, SLOPE, lens=lens_dev)()
     torch.cuda.synchronize()
     for b, L in enumerate(Ls):
         ref = sentinel(L * 3 * C, dev)  # compact copies: nothing behind the item
@@ -137,7 +137,7 @@ def test_pd_gather_ragged_grid_stride_loop_runs_more_than_once(dev):
     lens_dev = torch.tensor(lens, dtype=torch.int32, device=dev)
     buf = sentinel(2 * GUARD + B * T * 3 * C, dev)
     out = buf[GUARD:GUARD + B * T * 3 * C].view(B, T, 3 * C)
-    ops.pd_gather_ragged_op(x, d, lens_dev, (buf, GUARD), B, T, C, dil, SLOPE)()
+    ops.pd_gather_op(x, d, (buf, GUARD), B, T, C, dil, SLOPE, lens=lens_dev)()
     torch.cuda.synchronize()
     for b, L in enumerate(lens):
         ref = sentinel(L * 3 * C, dev)

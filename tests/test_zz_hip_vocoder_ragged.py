@@ -98,8 +98,8 @@ def test_resunit_ragged_is_the_dense_b1_call_bit_for_bit(dev, C, k, d, form, inp
 
     def ragged(lens_t, xin):
         buf, o = out_buffer(B, T, [(run_sum[b], L) for b, L in enumerate(lens_t.tolist())])
-        op = ops.RaggedResUnitOp(x=xin, out=(buf, GUARD), res2=(buf, GUARD) if inplace else None, n_batch=B, T=T,
-                                 lens=lens_t, **common)
+        op = ops.ResUnitOp(x=xin, out=(buf, GUARD), res2=(buf, GUARD) if inplace else None, n_batch=B, T=T,
+                           lens=lens_t, **common)
         op()
         torch.cuda.synchronize()
         return buf, o, op
@@ -135,7 +135,7 @@ def test_resunit_ragged_is_the_dense_b1_call_bit_for_bit(dev, C, k, d, form, inp
     # validation: no lengths / no params -> the error, nothing launched, nothing written
     vbuf, vout = out_buffer(B, T, [])
     before = vbuf.clone()
-    vop = ops.RaggedResUnitOp(x=x, out=(vbuf, GUARD), n_batch=B, T=T, lens=lens_dev, **dict(common, post_div=0.0))
+    vop = ops.ResUnitOp(x=x, out=(vbuf, GUARD), n_batch=B, T=T, lens=lens_dev, **dict(common, post_div=0.0))
     fn = _lib.lib().srn_hifigan_resunit_ragged
     assert fn(ctypes.byref(vop.p), None, stream()) == -1 and b"null lens" in _lib.lib().srn_last_error()
     assert fn(None, ctypes.c_void_p(lens_dev.data_ptr()), stream()) == -1
@@ -170,7 +170,7 @@ def test_out_conv_tanh_ragged_is_the_dense_b1_call_bit_for_bit(dev, C, k):
     lens_dev = torch.tensor(lens, dtype=torch.int32, device=dev)
     buf = sentinel(2 * GUARD + B * T, dev)
     y = buf[GUARD:GUARD + B * T].view(B, T)
-    ops.out_conv_tanh_ragged_op(x, w, bias, (buf, GUARD), lens_dev, B, T, C, k, 0.01)()
+    ops.out_conv_tanh_op(x, w, bias, (buf, GUARD), B, T, C, k, 0.01, lens=lens_dev)()
     torch.cuda.synchronize()
     for b, L in enumerate(lens):
         ref = sentinel(L, dev)
