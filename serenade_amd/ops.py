@@ -269,15 +269,12 @@ class TnGemmOp(_StructOp):
 
     __slots__ = ("_ws",)
 
-    def __init__(self, *, a, b, out, n_items, T_a, T_b, M, N, lda, ldb, ldc, shifts=(0,), stride=1, n_batch=1,
-                 n_head=1, a_bs=0, a_hs=0, a_is=0, b_bs=0, b_hs=0, b_is=0, out_bs=0, out_hs=0, alpha=1.0, n_inner=1,
-                 a_is2=0, b_is2=0, len_b=None, colsum=None, route=0):
-        self.name, self._fn = "srn_tn_gemm", _lib.lib().srn_tn_gemm
-        self.kw = dict(
-            a=a, b=b, out=out, n_items=n_items, T_a=T_a, T_b=T_b, M=M, N=N, lda=lda, ldb=ldb, ldc=ldc,
-            shifts=tuple(int(v) for v in shifts), stride=stride, n_batch=n_batch, n_head=n_head, a_bs=a_bs, a_hs=a_hs,
-            a_is=a_is, b_bs=b_bs, b_hs=b_hs, b_is=b_is, out_bs=out_bs, out_hs=out_hs, alpha=alpha, n_inner=n_inner,
-            a_is2=a_is2, b_is2=b_is2, len_b=len_b, colsum=colsum, route=route)
+    def __init__(self, **kw):
+        super().__init__("srn_tn_gemm", kw)
+
+    def _fill(self, *, a, b, out, n_items, T_a, T_b, M, N, lda, ldb, ldc, shifts=(0,), stride=1, n_batch=1,
+              n_head=1, a_bs=0, a_hs=0, a_is=0, b_bs=0, b_hs=0, b_is=0, out_bs=0, out_hs=0, alpha=1.0, n_inner=1,
+              a_is2=0, b_is2=0, len_b=None, colsum=None, route=0):
         p = _lib.SrnTnGemmParams()
         p.n_batch, p.n_head, p.n_items, p.T_a, p.T_b = n_batch, n_head, n_items, T_a, T_b
         p.stride, p.n_shifts, p.M, p.N = stride, len(shifts), M, N
@@ -291,13 +288,13 @@ class TnGemmOp(_StructOp):
             raise TypeError("TnGemmOp: len_b must be int32")
         p.len_b, p.colsum = _ptr(len_b), _ptr(colsum)
         p.route = int(route)  # _lib.TN_ROUTE_GENERAL: the general kernel only (testing / A-B timing)
-        need = int(_lib.lib().srn_tn_gemm_workspace_bytes(ctypes.byref(p)))
         self._ws = None
+        o = out[0] if isinstance(out, tuple) else out
+        need = int(_lib.lib().srn_tn_gemm_workspace_bytes(ctypes.byref(p))) if o.is_cuda else 0
         if need:
-            o = out[0] if isinstance(out, tuple) else out
             self._ws = tn_workspace(o.device, need)
             p.ws, p.ws_bytes = self._ws.data_ptr(), self._ws.numel()
-        self.p = p
+        return p
 
 
 class WorldOp(_StructOp):
@@ -511,7 +508,8 @@ def conv_taps(k, dilation=1, padding=None):
 def convtranspose_phases(w, stride, padding):
     """torch ConvTranspose1d weight (Ci, Co, k) -> per output phase r (out index = m*stride + r):
     (taps = input-row offsets relative to m, packed weight [Co][n_taps*Ci]).
-    out[o] = sum_i sum_k x[i] w[:, :, k] with o = i*stride - padding + k."""
+    out[o] = sum_i sum_k x[i] w[:, :, k] with o = i*stride - padding + k.
+    Slices, stack and reshape only: autograd flows through it (the training step packs its up-sampling weights here)."""
     ci, co, k = w.shape
     phases = []
     for r in range(stride):

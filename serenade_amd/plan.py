@@ -195,7 +195,8 @@ def attention_ops(qkv, Vt, S, out, lens, B, H, hd, T, precision):
     """S = Q K^T / sqrt(d) -> softmax over keys < len -> O = P V, chunk by chunk through S (attention_scores).
     qkv (B, T, 3 H hd): q | k row-major, as the QKV projection leaves them; Vt (B, H hd, rup(T, 32)): V^T, which that
     projection's transposed tail wrote (P V then contracts k-major rows like every other GEMM; its pad columns must be
-    zero, they meet exact zeros of the softmax); out (B, T, H hd); lens (B,) int32 valid keys per item."""
+    zero, they meet exact zeros of the softmax); out (B, T, H hd); lens (B,) int32 valid keys per item, or None.
+    The training step's attention node runs the same three ops with S holding all B * H pairs (one chunk)."""
     inner = H * hd
     Tp = rup(T, 32)
     ol = []
@@ -205,7 +206,7 @@ def attention_ops(qkv, Vt, S, out, lens, B, H, hd, T, precision):
                          T_out=T, C_in=hd, N=T, in0_bs=T * 3 * inner, in0_hs=hd, ld_in0=3 * inner,
                          w_bs=T * 3 * inner, w_hs=hd, ldw=3 * inner, out_bs=nh * T * Tp, out_hs=T * Tp,
                          ld_out=Tp, alpha=1.0 / math.sqrt(hd), precision=precision))
-        ol.append(ops.softmax_rows_op(S, (lens, b0), nb * nh, nh, T, Tp))
+        ol.append(ops.softmax_rows_op(S, lens if lens is None else (lens, b0), nb * nh, nh, T, Tp))
         ol.append(ConvOp(in0=S, w=(Vt, b0 * inner * Tp + h0 * hd * Tp), out=(out, b0 * T * inner + h0 * hd),
                          n_batch=nb, n_head=nh, T_in=T, T_out=T, C_in=Tp, N=hd, in0_bs=nh * T * Tp,
                          in0_hs=T * Tp, ld_in0=Tp, w_bs=inner * Tp, w_hs=hd * Tp, ldw=Tp, out_bs=T * inner,

@@ -5,6 +5,7 @@ strides, tap tables, phase decomposition) without a GPU: ``install()`` swaps the
 ``ops.ConvOp`` / ``ops.CallOp`` for these functions.  It is never importable from the product and it
 is NOT a fallback: on the GPU box the real library runs and is checked against the oracle.
 """
+import inspect
 import math
 
 import torch
@@ -543,8 +544,8 @@ def emul_resunit(kw):
 
 
 def emul_tn_gemm(kw):
-    """executable spec of srn_tn_gemm"""
-    g = kw.get
+    """executable spec of srn_tn_gemm; keywords the caller left out take the defaults of ops.TnGemmOp._fill"""
+    g = {**{k: p.default for k, p in inspect.signature(ops.TnGemmOp._fill).parameters.items()}, **kw}.get
     a, oa = _flat(g("a"))
     b, ob = _flat(g("b"))
     out, oo = _flat(g("out"))
@@ -608,16 +609,8 @@ class installed:
         ops.MultiCopyOp.__call__ = emul_multi_copy
         self._saved_tm = ops.TransposeMultiOp.__call__
         ops.TransposeMultiOp.__call__ = emul_transpose_multi
-        self._saved_tn = (ops.TnGemmOp.__call__, ops.TnGemmOp.__init__)
+        self._saved_tn = ops.TnGemmOp.__call__
         ops.TnGemmOp.__call__ = lambda self_, stream=None: emul_tn_gemm(self_.kw)
-
-        def tn_init(self_, **kw):  # no library call (workspace query) on the CPU
-            kw.setdefault("shifts", (0,))
-            for k, v in dict(stride=1, n_batch=1, n_head=1, a_bs=0, a_hs=0, a_is=0, b_bs=0, b_hs=0, b_is=0, out_bs=0,
-                             out_hs=0, alpha=1.0, n_inner=1, a_is2=0, b_is2=0, len_b=None, colsum=None).items():
-                kw.setdefault(k, v)
-            self_.name, self_.kw = "srn_tn_gemm", kw
-        ops.TnGemmOp.__init__ = tn_init
         ops.ConvOp.__call__ = lambda self_, stream=None: emul_conv(self_.kw)
         ops.ResUnitOp.__call__ = lambda self_, stream=None: emul_resunit(self_.kw)
         ops.CallOp.__call__ = lambda self_, stream=None: emul_call(self_.name, self_.targs)
@@ -629,6 +622,6 @@ class installed:
         ops.ConvOp.__call__, ops.CallOp.__call__, guards, ops.ResUnitOp.__call__ = self._saved
         ops.MultiCopyOp.__call__ = self._saved_mc
         ops.TransposeMultiOp.__call__ = self._saved_tm
-        ops.TnGemmOp.__call__, ops.TnGemmOp.__init__ = self._saved_tn
+        ops.TnGemmOp.__call__ = self._saved_tn
         for m, g in zip(self._mods, guards):
             m._require_cuda = g

@@ -63,7 +63,7 @@ def test_struct_layout_matches_c(tmp_path, name):
 
 
 def test_partial_sum_chunk_sizes_match_the_host_code():
-    """training.py sizes its partial-sum buffers as ceil(T / 32) rows per chunk; the library says the same (pure host
+    """training/functions.py sizes its partial-sum buffers as ceil(T / 32) rows per chunk; the library says the same (pure host
     functions, no GPU needed)"""
     from serenade_amd import _lib
     h = _lib.lib()

@@ -1,7 +1,7 @@
-"""SURVEY 8 f4 on the GPU: the estimator's training step (serenade_amd/training.py over libserenade_hip.so).
+"""SURVEY 8 f4 on the GPU: the estimator's training step (serenade_amd/training/ over libserenade_hip.so).
 
-  * the backward ops of training.py built on csrc/train.hip (conv, GroupNorm + Mish, row LayerNorm, attention core,
-    GEGLU, weight norm) against torch autograd of the op they differentiate, one shape each; the kernels of
+  * the backward ops of training/functions.py built on csrc/train.hip (conv, GroupNorm + Mish, row LayerNorm,
+    attention core, GEGLU, weight norm) against torch autograd of the op they differentiate, one shape each; the kernels of
     csrc/gst_train.hip are reached here only through the whole-model gradient test.  The per-kernel sweeps of both
     files (every C-ABI entry, edge shapes, float64 references, guard bands) are tests/test_hip_rowops.py;
   * loss + gradients of all 192 estimator parameters, d mu, d spks against the REFERENCE's own
@@ -18,6 +18,7 @@ import torch.nn.functional as F
 
 from oracle import serenade_oracle as O
 from serenade_amd import _lib, ops, training
+from serenade_amd.training.functions import _WeightNormPack
 from tests._weights import serenade_weights, sub
 from tests.test_training_emulated import _case, _golden_case, _oracle_grads, check_against_reference_gradients, rel
 
@@ -330,8 +331,8 @@ def test_captured_step_equals_eager_step(dev, B, L, lrs):
     """GraphedStep: the whole-model step captured as a hipGraph (device-side infill segment, clip factor and Adam bias
     corrections).  (a) With the weights frozen (lr = 0) every replay reproduces the eager step's losses and ALL
     gradients on three different batches -- torch's own multi-block reductions returned stale values from the second
-    replay on, which is why the step routes them through rocBLAS / srn_sumsq; (b) with the optimizer on, losses and
-    gradient norms track the eager run."""
+    replay on, which is why the step routes them through its own srn_dot / srn_colsum / srn_sumsq; (b) with the
+    optimizer on, losses and gradient norms track the eager run."""
     w = serenade_weights()  # sizes large enough for multi-block reductions
     g = torch.Generator().manual_seed(8)
     lens0 = torch.tensor([L - (L // 5) * (i % 3) for i in range(B)])
@@ -366,7 +367,8 @@ def test_captured_step_equals_eager_step(dev, B, L, lrs):
                 for k in cap.params:
                     ref = eager.params[k].grad
                     if ref.abs().max() > 1e-7:  # not the mathematically-zero key bias of the token attention
-                        # MIOpen's conv2d weight gradients (the GST's library path) are not run-to-run reproducible
+                        # the GST's conv2d weight gradients keep the bound of the library path they once took; they
+                        # are srn_tn_gemm launches now (training.functions._Conv2dS2)
                         tol_k = 2e-3 if k.startswith("gst.ref_enc.convs.") else 1e-4
                         assert rel(cap.params[k].grad.cpu(), ref.cpu()) < tol_k, (i, k)
         if lr == 0.0:
@@ -419,7 +421,7 @@ def test_memset_guard_sees_torch_reductions_and_clears_the_product_step(dev):
     ss = torch.zeros(1024, device=dev, dtype=torch.float64)
 
     def own():  # what AdamW._grad_norm does: srn_sumsq partial sums + a single-block sum of 1024 doubles
-        training._call("srn_sumsq", x, x.numel(), ss)
+        ops.call("srn_sumsq", x, x.numel(), ss)
         out["own"] = ss.sum()
 
     own()
@@ -542,7 +544,7 @@ def test_weight_norm_pack_against_torch(dev, shape):
     v = torch.randn(n, c, k, generator=g0).to(dev).requires_grad_(True)
     g = (torch.rand(n, 1, 1, generator=g0) + 0.5).to(dev).requires_grad_(True)
     co = torch.randn(n, k * c, generator=g0).to(dev)
-    w, wd = training._WeightNormPack.apply(v, g)
+    w, wd = _WeightNormPack.apply(v, g)
     (w * co).sum().backward()
     v2, g2 = v.detach().clone().double().requires_grad_(True), g.detach().clone().double().requires_grad_(True)
     ref = (v2 * (g2 / v2.reshape(n, -1).norm(dim=1).reshape(n, 1, 1))).permute(0, 2, 1).reshape(n, k * c)

@@ -84,7 +84,7 @@ def test_single_process_is_identity():
     assert waves[0] is w and ns[0].tolist() == [10, 10]
 
 
-# ---- f4: the DDP replacement of the training step (serenade_amd/training.py GradSync) ------------------------------
+# ---- f4: the DDP replacement of the training step (serenade_amd/training/ GradSync) ------------------------------
 def _grad_worker(rank, world, port, q):
     from serenade_amd import training
     os.environ["MASTER_ADDR"] = "127.0.0.1"

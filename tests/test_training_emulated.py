@@ -1,4 +1,4 @@
-"""SURVEY 8 f4 on the CPU: the estimator's training step (serenade_amd/training.py) through the kernel emulator,
+"""SURVEY 8 f4 on the CPU: the estimator's training step (serenade_amd/training/) through the kernel emulator,
 against autograd through the CPU oracle's `cfm_compute_loss` (flow_matching.py:95-133 over decoder.py) on the same
 weights, inputs and random draws: the loss value and all 192 parameter gradients, d mu and d spks; then one clipped
 AdamW step against torch.optim.AdamW + clip_grad_norm_ (trainers/ssc.py:86-96)."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool (GPU): which lines of serenade_amd/training.py launch torch's own kernels (copies, adds, fills ...)
+"""Developer tool (GPU): which lines of serenade_amd/training/ launch torch's own kernels (copies, adds, fills ...)
 during one eager training step, and what they cost.  torch.profiler with stacks; own kernels (srn_* calls through
 ctypes) do not show up as aten ops and are left out on purpose.
 
@@ -49,7 +49,7 @@ def main():
             continue
         where = "?"
         for fr in ev.stack or ():
-            if "serenade_amd/training.py" in fr:
+            if "serenade_amd/training/" in fr:
                 where = fr.split("serenade_amd/")[-1]
                 break
         if where == "?":  # no python stacks on this stack: the op and its operand shapes identify the call site
