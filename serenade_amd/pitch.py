@@ -56,8 +56,9 @@ def pyin_frames(lengths, frame_length=2048, hop_length=None, center=True):
     return [1 + (int(n) + 2 * pad - frame_length) // hop for n in lengths]
 
 
-def _check(sr, fmin, fmax, frame_length, win_length, hop_length, n_thresholds, resolution, center, pad_mode):
-    """librosa's __check_yin_params, then the limits of the kernels"""
+def _check(sr, fmin, fmax, frame_length, win_length, hop_length, n_thresholds, resolution, center, pad_mode,
+           max_transition_rate=35.92):
+    """librosa's __check_yin_params and transition_local's width rule, then the limits of the kernels"""
     if fmin is None or fmax is None:
         raise ValueError("pyin: both fmin and fmax must be provided")
     if fmax > sr / 2:
@@ -79,6 +80,11 @@ def _check(sr, fmin, fmax, frame_length, win_length, hop_length, n_thresholds, r
         raise ValueError(f"pyin: n_thresholds={n_thresholds} and resolution={resolution} must be positive")
     if center and pad_mode != "constant":
         raise ValueError(f"pyin: pad_mode {pad_mode!r} is not supported (librosa 0.10's default 'constant' is)")
+    g = pyin_geometry(fmin=fmin, fmax=fmax, sr=sr, frame_length=frame_length, win_length=win_length,
+                      hop_length=hop_length, resolution=resolution, max_transition_rate=max_transition_rate)
+    if not 1 <= g["width"] <= g["n_bins"]:  # librosa: transition_local's "width must be between 1 and n_states"
+        raise ValueError(f"pyin: transition width {g['width']} (max_transition_rate={max_transition_rate} at "
+                         f"hop_length={hop_length}) must lie between 1 and the {g['n_bins']} pitch bins")
 
 
 def transition_local(n_states, width):
@@ -208,7 +214,8 @@ def pyin(wave, lengths=None, *, fmin, fmax, sr=22050, frame_length=2048, win_len
         win_length = frame_length // 2
     if hop_length is None:
         hop_length = frame_length // 4
-    _check(sr, fmin, fmax, frame_length, win_length, hop_length, n_thresholds, resolution, center, pad_mode)
+    _check(sr, fmin, fmax, frame_length, win_length, hop_length, n_thresholds, resolution, center, pad_mode,
+           max_transition_rate)
     _require_cuda(wave)
     one = wave.ndim == 1
     x = wave.reshape(1, -1) if one else wave

@@ -170,8 +170,10 @@ def obs_matrix(voiced, vp):
 
 def pyin(y, *, fmin, fmax, sr=22050, frame_length=2048, win_length=None, hop_length=None, n_thresholds=100,
          beta_parameters=(2, 18), boltzmann_parameter=2, resolution=0.1, max_transition_rate=35.92, switch_prob=0.01,
-         no_trough_prob=0.01, fill_na=np.nan, center=True):
-    """librosa.pyin of one 1-D signal -> (f0, voiced_flag, voiced_prob, near_tie) with near_tie per frame"""
+         no_trough_prob=0.01, fill_na=np.nan, center=True, stages=False):
+    """librosa.pyin of one 1-D signal -> (f0, voiced_flag, voiced_prob, near_tie) with near_tie per frame;
+    stages=True appends a dict of what lies between: the cmnd rows `yin`, the voiced observation matrix `voiced` and
+    the decoded `states`"""
     g = geometry(fmin=fmin, fmax=fmax, sr=sr, frame_length=frame_length, win_length=win_length,
                  hop_length=hop_length, resolution=resolution, max_transition_rate=max_transition_rate)
     fr = frames_of(y, frame_length, g["hop_length"], center)
@@ -190,4 +192,6 @@ def pyin(y, *, fmin, fmax, sr=22050, frame_length=2048, win_length=None, hop_len
     flag = states < n
     if fill_na is not None:
         f0[~flag] = fill_na
+    if stages:
+        return f0, flag, vp, near, dict(yin=yin, voiced=voiced, states=states, geometry=g)
     return f0, flag, vp, near

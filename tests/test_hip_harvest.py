@@ -2,7 +2,8 @@
 every stage fed by the restatement's previous stage, end to end on tones, glides, vibrato, note sequences, an octave
 leap, noise, silence and a short item at three parameter sets, the ground truth of the synthetic signals, other sampling
 rates, exact ragged batching, the frame-period pick, a 6 s item and extract_f0.  Signals the restatement flags as
-carrying a near-tie are left out of the end-to-end comparison; tests/test_harvest_host.py bounds how many may be."""
+carrying a near-tie are left out of the end-to-end comparison; tests/test_harvest_host.py bounds how many may be.
+Tile-boundary lengths, chunked launches and synthetic inputs of every stage: tests/test_zzzz_hip_harvest_sweep.py."""
 import numpy as np
 import pytest
 import torch

@@ -1,6 +1,7 @@
 """pYIN on the MI355X (serenade_amd/pitch.py + pyin.hip) against the float64 restatement tests/_pyin_ref.py: the
 transcriber's settings and librosa's defaults on tones, glides, note sequences, octave leaps, noise, silence and short
-items; the Viterbi alone; exact ragged batching; a 60 s item; and the transcriber's decoder fed by reference_f0."""
+items; the Viterbi alone; exact ragged batching; a 60 s item; and the transcriber's decoder fed by reference_f0.
+Edge geometries, parameters off their defaults and the observation matrix itself: tests/test_zzzz_hip_pyin_sweep.py."""
 import json
 
 import numpy as np

@@ -117,6 +117,7 @@ def test_restatement_tracks_a_harmonic_tone_and_silence():
     dict(fmin=65, fmax=2093, sr=16000, win_length=1024),      # win_length >= frame_length
     dict(fmin=65, fmax=200, sr=16000, frame_length=256, win_length=200),  # the period range does not fit
     dict(fmin=65, fmax=2093, sr=16000, pad_mode="reflect"),   # only librosa 0.10's constant padding
+    dict(fmin=100, fmax=800, sr=8000, frame_length=512, win_length=300, hop_length=700),  # width 381 over 361 bins
 ])
 def test_pyin_rejects_bad_parameters(kw):
     kw = dict(dict(frame_length=1024), **kw)
