@@ -323,6 +323,19 @@ int srn_pd_gather_ragged(const float* x, const float* d, const int32_t* lens, fl
  * h -> W_hh h.  w_hh_t (H, 3H) = W_hh transposed. */
 int srn_gru_recur_last(const float* gi, const float* w_hh_t, const float* b_hh, float* h, int B, int T, int H,
                        void* stream);
+/* The same recurrence over a ragged batch: gi keeps its (B, T_cap, 3H) strides, item b's recurrence ends after
+ * min(n_steps[b], T_cap) steps (n_steps: device, B int32, each >= 1).  h[b] is bit for bit what srn_gru_recur_last gives
+ * on that item's own (1, n_steps[b], 3H) rows: one kernel, stated once, runs both.  Rows of gi at or past an item's step
+ * count are not loaded, whatever they hold (NaN included).  Argument checks as the dense call, plus a non-NULL
+ * `n_steps`. */
+int srn_gru_recur_last_ragged(const float* gi, const float* w_hh_t, const float* b_hh, float* h, const int32_t* n_steps,
+                              int B, int T_cap, int H, void* stream);
+/* The mask of the style encoder's ragged batch (time is the head axis of its Conv2d launches, which len_in / len_out
+ * do not reach): for item b, rows h in [n_rows[b], rows_cap) of x + b * bs, n_cols contiguous floats each and rows back
+ * to back, become +0.0; rows below n_rows[b] are not touched, n_rows[b] >= rows_cap writes nothing (n_rows: device, B
+ * int32, each >= 0).  NULL pointers, non-positive sizes and items that overlap (bs < rows_cap * n_cols with B > 1) are
+ * refused. */
+int srn_zero_rows_ragged(float* x, int64_t bs, int n_cols, const int32_t* n_rows, int B, int rows_cap, void* stream);
 
 /* StyleTokenLayer (style_encoder.py:235-252 + gst/attention.py:110-184,298-300): ref (B, Dq) -> out (B, F), with its
  * input-independent parts formed at weight-packing time: k, v (n_tok, F) = tanh(embs) W_k^T + b_k / W_v^T + b_v;

@@ -148,6 +148,8 @@ _SIGS = {
     "srn_logmel_ragged": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
     "srn_loudness_ragged": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, _P]),
     "srn_gru_recur_last": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "srn_gru_recur_last_ragged": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "srn_zero_rows_ragged": (c_int, [_P, c_int64, c_int, _P, c_int, c_int, _P]),
     "srn_style_token_attention_kv": (c_int, [_P] * 8 + [c_int] * 5 + [_P]),
     "srn_rowln_fwd": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int, c_float, _P]),
     "srn_rowln_bwd": (c_int, [_P, _P, _P, c_int64, _P, _P, c_int, c_int, c_int, c_float, _P]),

@@ -15,7 +15,10 @@ item's padded length (decoder.py:71-77), so naive padding into a batch would cha
 converts all styles of an utterance in one *exact* ragged batch (`Serenade.inference_ragged`: per-item GroupNorm
 statistics, per-item reflection padding, per-item prompt / source offsets), whose results equal the loop's;
 `--batch-utterances N` extends the batch over N source utterances of different lengths; `--ragged-vocoder` then
-vocodes the batch's mels in one exact ragged call too (`Vocoder.decode_ragged`) instead of one call per length.  With
+vocodes the batch's mels in one exact ragged call too (`Vocoder.decode_ragged`) instead of one call per length.
+`--ragged-plan` runs every conversion, batched or one by one, on the conversion model's length-bucketed plan
+(`Serenade.inference_ragged(bucket=models.RAGGED_BUCKET)`: lengths are data, one plan and one captured graph per batch
+size and 64-row bucket of the longest prompt + source) instead of one plan per distinct set of lengths.  With
 `torchrun --nproc-per-node N` the utterance list is split contiguously over the ranks (one GPU each).
 """
 import argparse
@@ -91,6 +94,11 @@ def build_parser():
                    help="(MI355X build only; with --batch-styles / --batch-utterances) vocode the mels of a batch in "
                         "ONE ragged HiFi-GAN call (Vocoder.decode_ragged: lengths are data, every item is computed as "
                         "its own B = 1 call) instead of one call, plan and captured graph per distinct length")
+    p.add_argument("--ragged-plan", action="store_true",
+                   help="(MI355X build only) run the conversion model with lengths as data: one plan, and one captured "
+                        "graph, per batch size and 64-row bucket of the longest prompt + source "
+                        "(Serenade.inference_ragged(bucket=)), for batches and for the one-by-one loop alike, instead "
+                        "of a new plan for every new set of lengths; every item is still computed as its own B = 1 call")
     p.add_argument("--sifigan-checkpoint", type=str, default=None,
                    help="(MI355X build only) also run the recipe's stage 9 in this process: re-analyse every converted "
                         "waveform on the GPU (serenade_amd.world.Analyzer) and write NAME_sifigan.wav from this SiFiGAN "
@@ -220,10 +228,10 @@ class DecodeJob:
         if not jobs:
             return 0
         out = self.args.outdir
+        bucket = serenade_amd.models.RAGGED_BUCKET if getattr(self.args, "ragged_plan", False) else None
+        as_item = lambda x, sc, ld, r: (x[0], sc[0], ld[0], r["cvec"][0], r["mel"][0], r["score"][0], r["loud"][0])
         if batched and len(jobs) > 1:
-            mels = self.model.inference_ragged(
-                [(x[0], sc[0], ld[0], r["cvec"][0], r["mel"][0], r["score"][0], r["loud"][0])
-                 for _, _, x, sc, ld, r, _ in jobs])
+            mels = self.model.inference_ragged([as_item(x, sc, ld, r) for _, _, x, sc, ld, r, _ in jobs], bucket=bucket)
             if self.args.ragged_vocoder:
                 waves = self.vocoder.decode_ragged(mels)
             else:
@@ -237,6 +245,10 @@ class DecodeJob:
         else:
             waves = []
             for _, _, x, sc, ld, r, _ in jobs:
+                if bucket is not None:  # a batch of one on the bucketed plan: the same draw, the same result
+                    mel = self.model.inference_ragged([as_item(x, sc, ld, r)], bucket=bucket)[0]
+                    waves.append(self.vocoder.decode(mel)[0])
+                    continue
                 lengths = torch.tensor([x.shape[1]], dtype=torch.long)
                 mel = self.model.inference(x, lengths, sc, ld, r["cvec"], r["lens"], r["mel"], r["score"], r["loud"])
                 waves.append(self.vocoder.decode(mel.squeeze(0) if mel.dim() == 3 else mel)[0])

@@ -23,7 +23,8 @@ import torch.nn as nn
 
 from . import _shapes, ops
 from .ops import ACT_LEAKY, ACT_MISH, ACT_SILU, RES_ADD, RES_AXPY, ConvOp
-from .plan import attention_ops, attention_scores, conv_op, dev_f32, linear_op, lru_get, rup, tensors_of
+from .plan import (StridedLengthTable, attention_ops, attention_scores, conv_op, dev_f32, item_lengths, linear_op,
+                   lru_get, rup, tensors_of)
 from .plan import require_cuda as _require_cuda
 from .utils.masking import make_non_pad_mask
 
@@ -653,8 +654,18 @@ class StyleEncoder(_Packed):
             self._packed = P
         return self._packed
 
-    def build_ops(self, speech, B, T, out):
-        """speech (B, T, idim) device tensor -> out (B, gst_token_dim)."""
+    def length_table(self, B):
+        """the per-item heights of a ragged batch at every conv layer (build_ops' `lens`), all zero until set_lengths"""
+        return StridedLengthTable(len(self.chans), B, self._device())
+
+    def build_ops(self, speech, B, T, out, lens=None):
+        """speech (B, T, idim) device tensor -> out (B, gst_token_dim).
+        lens (`length_table(B)`): the items hold lens.rows[0][b] <= T prompt rows each, read when the ops RUN; item b's
+        style vector is then what this encoder gives for that prompt alone.  Time is the head axis of the Conv2d
+        launches, which a conv's own len_in / len_out do not reach, so the prompt image and every layer output but the
+        last are masked behind the item's height (srn_zero_rows_ragged): the next layer's kernel row 2 reads the row
+        just behind an odd height and must find the zero padding there that the item alone has, not ReLU(shift) or an
+        earlier batch's leftovers.  The last layer feeds the GRU, which stops at the item's own step count."""
         P = self.packed()
         dev = self._device()
         ol = []
@@ -667,6 +678,8 @@ class StyleEncoder(_Packed):
         c0 = P["convs"][0]["cpad"]
         cur = torch.zeros(B, H + 2, W, c0, device=dev, dtype=torch.float32)
         ol.append(ops.copy_channels_op(speech, T * W, 1, 0, (cur, W * c0), (H + 2) * W * c0, c0, 0, B, T * W, 1))
+        if lens is not None:
+            ol.append(ops.zero_rows_ragged_op((cur, W * c0), (H + 2) * W * c0, W * c0, lens.rows[0], B, H))
         n_l = len(P["convs"])
         for li, c in enumerate(P["convs"]):
             Ho, Wo, Co, Cp = (H - 1) // 2 + 1, (W - 1) // 2 + 1, c["co"], c["cpad"]
@@ -685,6 +698,8 @@ class StyleEncoder(_Packed):
                 if j == 2:
                     kw.update(post=ops.POST_RELU)
                 ol.append(ConvOp(**kw))
+            if lens is not None and not last:
+                ol.append(ops.zero_rows_ragged_op(yo, (Ho + 2) * Wo * Co, Wo * Co, lens.rows[li + 1], B, Ho))
             cur, H, W, Ci = y, Ho, Wo, Co
         ref = torch.zeros(B, self.gru_units, device=dev, dtype=torch.float32)
         # GRU: input projection of all (b, t) rows as one contraction over the chip, then the short recurrence
@@ -693,7 +708,11 @@ class StyleEncoder(_Packed):
             raise ValueError(f"GRU input width {I} (mel bins left x channels) must be a multiple of 4")
         gi = torch.zeros(B, H, G3, device=dev, dtype=torch.float32)
         ol.append(linear_op(cur, B * H, I, P["w_ih"], P["b_ih"], gi, G3))
-        ol.append(ops.gru_recur_last_op(gi, P["w_hh_t"], P["b_hh"], ref, B, H, self.gru_units))
+        if lens is None:
+            ol.append(ops.gru_recur_last_op(gi, P["w_hh_t"], P["b_hh"], ref, B, H, self.gru_units))
+        else:  # the projection above ran over all B * H rows; the recurrence reads an item's first lens.rows[-1][b]
+            ol.append(ops.gru_recur_last_ragged_op(gi, P["w_hh_t"], P["b_hh"], ref, lens.rows[n_l], B, H,
+                                                   self.gru_units))
         ol.append(ops.style_token_attention_kv_op(ref, P["wq_t"], P["bq"], P["tok_k"], P["tok_v"], P["wo_t"], P["bo"],
                                                   out, B, self.gru_units, self.gst_tokens, self.gst_token_dim,
                                                   self.gst_heads))
@@ -701,10 +720,18 @@ class StyleEncoder(_Packed):
         return ol
 
     @torch.no_grad()
-    def forward(self, speech):
-        """(B, Lmax, idim) -> (B, gst_token_dim)   (style_encoder.py:78-91)."""
+    def forward(self, speech, lengths=None):
+        """(B, Lmax, idim) -> (B, gst_token_dim)   (style_encoder.py:78-91).
+        lengths (B row counts in [1, Lmax]): a padded batch of prompts; item b's vector is what forward gives for
+        speech[b:b + 1, :lengths[b]], whatever the rows behind an item hold.  One plan per (B, Lmax) serves every set
+        of lengths."""
         _require_cuda(speech, "StyleEncoder.forward")
         B, T, _ = speech.shape
+        if lengths is not None:
+            lens = item_lengths(lengths, B, T, "StyleEncoder.forward")
+            key = ("ragged", B, T, ops.DEFAULT_PRECISION)
+            rp = lru_get(self._plans, key, 4, lambda: StyleEncoderRaggedPlan(self, B, T))
+            return rp.run(speech, lens)
         out = torch.empty(B, self.gst_token_dim, device=speech.device, dtype=torch.float32)
         ol = self.build_ops(speech.detach().to(torch.float32).contiguous(), B, T, out)
         for op in ol:
@@ -712,9 +739,31 @@ class StyleEncoder(_Packed):
         return out
 
 
+class StyleEncoderRaggedPlan:
+    """`StyleEncoder.forward(speech, lengths=)`: staging buffer, length table and the batched op list for one
+    (B, T_cap); the lengths are rewritten in place before each run."""
+
+    def __init__(self, gst, B, T_cap):
+        dev = gst._device()
+        self.speech = torch.zeros(B, T_cap, gst.idim, device=dev, dtype=torch.float32)
+        self.out = torch.zeros(B, gst.gst_token_dim, device=dev, dtype=torch.float32)
+        self.table = gst.length_table(B)
+        self.ops = gst.build_ops(self.speech, B, T_cap, self.out, lens=self.table)
+
+    def run(self, speech, lens):
+        self.speech.copy_(speech.detach())
+        self.table.set_lengths(lens)
+        for op in self.ops:
+            op()
+        return self.out.clone()
+
+
 # =====================================================================================
 #  Serenade
 # =====================================================================================
+RAGGED_BUCKET = 64  # rows: the length bucket of `Serenade.inference_ragged(bucket=)` that the decode CLI uses
+
+
 class Serenade(_Packed):
     """serenade/models/serenade.py:35-221."""
 
@@ -767,15 +816,31 @@ class Serenade(_Packed):
         return ret
 
     @torch.inference_mode()
-    def inference_ragged(self, items, n_timesteps=10, temperature=0.667, noises=None):
+    def inference_ragged(self, items, n_timesteps=10, temperature=0.667, noises=None, bucket=None):
         """Several conversions in ONE batch, each exactly what `inference` returns for it alone (B = 1): `items` is a
         list of (x (T,in), midi (T,1), lft (T,1), ref_x (R,in), ref_logmel (R,out), ref_midi (R,1), ref_lft (R,1));
         T and R may differ per item.  Returns a list of (T, out) tensors.  `noises` (optional list of (out, R + T)
         tensors) replaces the draws; by default the noise of item b is drawn on the CPU generator in item order, as a
-        loop of B = 1 calls would (flow_matching.py:57-60).  This is what the decode CLI batches its styles with."""
+        loop of B = 1 calls would (flow_matching.py:57-60).  This is what the decode CLI batches its styles with.
+        bucket (int >= 1; the CLI passes RAGGED_BUCKET): lengths as data -- one plan, and with graphs on one capture,
+        per (B, longest R + T rounded up to `bucket`) instead of one per tuple of shapes (BucketedInferencePlan)."""
         if len(items) == 0:
             raise ValueError("Serenade.inference_ragged: no items")
+        if bucket is not None:
+            if isinstance(bucket, bool) or not isinstance(bucket, int) or bucket < 1:
+                raise ValueError(f"Serenade.inference_ragged: bucket must be an int >= 1, not {bucket!r}")
+            shapes = _ragged_item_shapes(items)
         _require_cuda(items[0][0], "Serenade.inference_ragged")
+        if bucket is not None:
+            L_cap = rup(max(t + r for t, r in shapes), bucket)
+            key = ("ragged-bucket", len(items), L_cap, n_timesteps, ops.DEFAULT_PRECISION, ops.attention_precision())
+            rp = lru_get(self._plans, key, 4, lambda: BucketedInferencePlan(self, len(items), L_cap, n_timesteps))
+            rp.set_lengths(shapes)
+            rp.load(items)
+            if noises is None:
+                dev = items[0][0].device
+                noises = [torch.randn((1, self.output_dim, t + r)).to(dev)[0] * temperature for t, r in shapes]
+            return rp.run(noises)
         shapes = tuple((int(it[0].shape[0]), int(it[3].shape[0])) for it in items)
         key = ("ragged", shapes, n_timesteps, ops.DEFAULT_PRECISION, ops.attention_precision())
         rp = lru_get(self._plans, key, 4, lambda: RaggedInferencePlan(self, shapes, n_timesteps))
@@ -874,6 +939,85 @@ class RaggedInferencePlan:
         pl.run()
         out = pl.read_out()  # (B, oc, Lm)
         return [out[b, :, r:r + t].t().contiguous() for b, (t, r) in enumerate(self.shapes)]
+
+
+RAGGED_MIN_ROWS = 4  # the content encoder's ReflectionPad1d(3) needs more than 3 rows of the longest track
+
+
+def _ragged_item_shapes(items):
+    """[(T_b, R_b)] of `inference_ragged`'s items, or ValueError: every track of an item must have the item's row
+    count, and the lengths must be ones the shape-keyed plan accepts (no empty track; the longest source and the
+    longest prompt of the batch carry the encoder's reflection padding)."""
+    shapes = []
+    for b, it in enumerate(items):
+        if len(it) != 7:
+            raise ValueError(f"Serenade.inference_ragged: item {b} has {len(it)} tensors, not (x, midi, lft, ref_x, "
+                             "ref_logmel, ref_midi, ref_lft)")
+        t, r = int(it[0].shape[0]), int(it[3].shape[0])
+        for name, src, n in (("midi", it[1], t), ("lft", it[2], t), ("ref_logmel", it[4], r), ("ref_midi", it[5], r),
+                             ("ref_lft", it[6], r)):
+            if int(src.shape[0]) != n:
+                raise ValueError(f"Serenade.inference_ragged: item {b}: {name} has {int(src.shape[0])} rows, its "
+                                 f"{'prompt' if name.startswith('ref') else 'source'} has {n}")
+        if t < 1 or r < 1:
+            raise ValueError(f"Serenade.inference_ragged: item {b} has an empty track (T = {t}, R = {r})")
+        shapes.append((t, r))
+    if max(t for t, _ in shapes) < RAGGED_MIN_ROWS or max(r for _, r in shapes) < RAGGED_MIN_ROWS:
+        raise ValueError(f"Serenade.inference_ragged: the longest source and the longest prompt need at least "
+                         f"{RAGGED_MIN_ROWS} rows each (reflection padding), got (T, R) = {shapes}")
+    return shapes
+
+
+class BucketedInferencePlan(RaggedInferencePlan):
+    """`Serenade.inference_ragged(bucket=)`: RaggedInferencePlan with every length as DATA, one plan per (B, L_cap)
+    where L_cap is the batch's longest R_b + T_b rounded up to the bucket.  The source and the prompt staging buffers
+    have L_cap rows each (either track of an item may be as long as the cap), the estimator plan is (B, L_cap)
+    `exact_ragged`, and the style encoder is ONE batched op list over (B, L_cap) prompt rows with per-item heights
+    (`StyleEncoder.build_ops(lens=)`), not one list per item.  `set_lengths` rewrites t_len, r_len, the style encoder's
+    table and the estimator's lengths in place before a run -- outside the captured graphs, whose nodes carry only the
+    buffers' addresses -- so one capture serves every batch of the bucket.  What lies behind an item's rows in any
+    buffer (an earlier batch's leftovers) is never read as data.  `load` and `run` are the shape-keyed plan's."""
+
+    def __init__(self, model, B, L_cap, n_timesteps):
+        dev = model._device()
+        self.B, self.Lm, self.shapes = B, L_cap, None
+        oc, ec = model.output_dim, model.encoder_channels
+        self.pl = pl = model.cfm_decoder.estimator.plan(B, L_cap, n_timesteps, euler=True, exact_ragged=True)
+        h0, cp0 = pl.h0, pl.h0.shape[2]
+        f = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
+        self.x, self.ref_x = f(B, L_cap, model.input_dim), f(B, L_cap, model.input_dim)
+        self.ref_mel = f(B, L_cap, oc)
+        self.midi, self.lft, self.ref_midi, self.ref_lft = f(B, L_cap, 1), f(B, L_cap, 1), f(B, L_cap, 1), f(B, L_cap, 1)
+        self.zeros, self.enc_src = f(B, L_cap, oc), f(B, L_cap, ec)
+        self.t_len = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.r_len = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.gst_lens = model.gst.length_table(B)
+        c0 = oc + ec
+        ol = model.encoder.build_ops(self.ref_x, B, L_cap, (h0, oc), L_cap * cp0, cp0, lens=self.r_len)
+        ol.append(ops.copy_channels_op(self.ref_midi, L_cap, 1, 0, h0, L_cap * cp0, cp0, c0, B, L_cap, 1))
+        ol.append(ops.copy_channels_op(self.ref_lft, L_cap, 1, 0, h0, L_cap * cp0, cp0, c0 + 1, B, L_cap, 1))
+        ol.append(ops.copy_channels_op(self.ref_mel, L_cap * oc, oc, 0, h0, L_cap * cp0, cp0, c0 + 2, B, L_cap, oc))
+        # source rows start where the item's prompt ends; R_b + T_b <= L_cap keeps them inside the item's rows of h0
+        ol += model.encoder.build_ops(self.x, B, L_cap, self.enc_src, L_cap * ec, ec, lens=self.t_len)
+        for src, ch, width in ((self.enc_src, oc, ec), (self.midi, c0, 1), (self.lft, c0 + 1, 1),
+                               (self.zeros, c0 + 2, oc)):
+            ol.append(ops.scatter_rows_op(src, L_cap * width, width, h0, L_cap * cp0, cp0, ch, self.r_len, self.t_len, B,
+                                          L_cap, width))
+        ol += model.gst.build_ops(self.ref_mel, B, L_cap, pl.spk, lens=self.gst_lens)
+        self.ops = ol
+        self._runner = ops.GraphRunner(lambda: self.ops)
+        self._sched = euler_schedule(n_timesteps)
+        self._z = f(B, oc, L_cap)
+
+    def set_lengths(self, shapes):
+        """shapes: B pairs (T_b, R_b) with R_b + T_b <= L_cap (validated by the caller, _ragged_item_shapes)"""
+        shapes = [(int(t), int(r)) for t, r in shapes]
+        assert len(shapes) == self.B and max(t + r for t, r in shapes) <= self.Lm
+        self.shapes = shapes
+        self.t_len.copy_(torch.tensor([t for t, _ in shapes], dtype=torch.int32))
+        self.r_len.copy_(torch.tensor([r for _, r in shapes], dtype=torch.int32))
+        self.gst_lens.set_lengths([r for _, r in shapes])
+        self.pl.set_lens(torch.tensor([t + r for t, r in shapes]))
 
 
 class InferencePlan:

@@ -484,6 +484,19 @@ def gru_recur_last_op(gi, w_hh_t, b_hh, h, B, T, H):
     return CallOp("srn_gru_recur_last", (gi, w_hh_t, b_hh, h, B, T, H))
 
 
+def gru_recur_last_ragged_op(gi, w_hh_t, b_hh, h, n_steps, B, T_cap, H):
+    """n_steps (_item_lens): item b's recurrence ends after n_steps[b] of its T_cap rows of gi"""
+    n_steps = _item_lens(n_steps, B, "gru_recur_last_ragged_op")
+    return CallOp("srn_gru_recur_last_ragged", (gi, w_hh_t, b_hh, h, n_steps, B, T_cap, H))
+
+
+def zero_rows_ragged_op(x, bs, n_cols, n_rows, B, rows_cap):
+    """n_rows (_item_lens): rows [n_rows[b], rows_cap) of item b of x (n_cols floats each, items bs floats apart)
+    become zero"""
+    n_rows = _item_lens(n_rows, B, "zero_rows_ragged_op")
+    return CallOp("srn_zero_rows_ragged", (x, bs, n_cols, n_rows, B, rows_cap))
+
+
 def style_token_attention_kv_op(ref, wq_t, bq, k, v, wo_t, bo, out, B, Dq, n_tok, F, n_head):
     return CallOp("srn_style_token_attention_kv", (ref, wq_t, bq, k, v, wo_t, bo, out, B, Dq, n_tok, F, n_head))
 

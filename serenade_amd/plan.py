@@ -1,6 +1,6 @@
 """What every plan builder shares: the small helpers, the op builders that several plans repeat (batched conv, dense
-layer, chunked self-attention, the stages and the length table of the HiFi-GAN / SiFiGAN generators) and the input /
-state-dict checks of the waveform front-ends.  A plan is a list of
+layer, chunked self-attention, the stages and the length table of the HiFi-GAN / SiFiGAN generators, the height table
+of the ragged style encoder) and the input / state-dict checks of the waveform front-ends.  A plan is a list of
 prebuilt C-ABI calls (``ops.ConvOp`` / ``ops.CallOp``) over preallocated buffers; nothing here launches anything.
 """
 import math
@@ -161,6 +161,26 @@ class LengthTable:
         """lengths: B frame counts in [1, T_cap] (validated by the caller, item_lengths)"""
         host = torch.tensor([[int(n) * s for n in lengths] for s in self.scales], dtype=torch.int32)
         self.lens.copy_(host)
+
+
+class StridedLengthTable:
+    """the heights of a ragged batch through a stack of `n_layers` stride-2 convs (k3, p1: H -> (H - 1) // 2 + 1), kept
+    the way LengthTable keeps a generator's: `lens` ONE (n_layers + 1, B) int32 device tensor, row 0 the items' own
+    row counts, `rows` its (B,) rows, which the ops read when they run.  set_lengths() rewrites the tensor in place --
+    outside the captured graph, whose nodes only carry its address."""
+
+    def __init__(self, n_layers, B, dev):
+        self.n_layers, self.B = n_layers, B
+        self.lens = torch.zeros(n_layers + 1, B, dtype=torch.int32, device=dev)
+        self.rows = list(self.lens.unbind(0))
+
+    def set_lengths(self, lengths):
+        """lengths: B row counts in [1, T_cap] (validated by the caller, item_lengths)"""
+        table = [[int(n) for n in lengths]]
+        assert len(table[0]) == self.B
+        for _ in range(self.n_layers):
+            table.append([(h - 1) // 2 + 1 for h in table[-1]])
+        self.lens.copy_(torch.tensor(table, dtype=torch.int32))
 
 
 # ---------------------------------------------------------------------------------------------- self-attention
