@@ -250,6 +250,15 @@ int srn_out_conv_tanh(const float* x, const float* w, const float* bias, float* 
  * L_b <= t < T.  Kernel choice as in the dense call (C = 32, k = 7 specialised; generic otherwise). */
 int srn_out_conv_tanh_ragged(const float* x, const float* w, const float* bias, float* y, const int32_t* lens, int B,
                              int T, int C, int k, float slope, void* stream);
+/* The output stage of a causal generator: LeakyReLU(slope) -> CausalConv1d(C -> 1, k) -> tanh (hifigan.py:151-162,
+ * vocoder/layers/causal_conv.py:11-41).  x (B, (k - 1) + T, C): per item k - 1 history rows, then the T rows of this
+ * call; w (k, C); y (B, T):
+ *     y[b, t] = tanh(bias + sum_i w[i] . LeakyReLU(x[b, t + i])),  i < k.
+ * History rows of zeros are the conv's causal zero padding (LeakyReLU(0) = 0), so the start of an utterance needs no
+ * length: the one-shot call passes zeros, a call in mid-stream the last k - 1 rows of the call before.  Kernel choice
+ * as in the dense call (C = 32, k = 7 specialised; generic otherwise), argument checks as the dense call. */
+int srn_out_conv_tanh_causal(const float* x, const float* w, const float* bias, float* y, int B, int T, int C, int k,
+                             float slope, void* stream);
 
 /*
  * One residual unit of HiFiGANResidualBlock with use_additional_convs (residual_block.py:243-258, loop body):
@@ -266,7 +275,8 @@ int srn_out_conv_tanh_ragged(const float* x, const float* w, const float* bias, 
  */
 typedef struct SrnResUnitParams {
   int32_t n_batch, T, C;
-  int32_t k, dilation;      /* conv1: kernel k, dilation `dilation`; conv2: kernel k, dilation 1; both "same" padded */
+  int32_t k, dilation;      /* conv1: kernel k, dilation `dilation`; conv2: kernel k, dilation 1; both "same" padded
+                             * (srn_hifigan_resunit_causal: both left-padded) */
   float slope;              /* LeakyReLU negative slope in front of both convs */
   const float* x; int64_t x_bs;
   const float* w1; const float* b1; const float* w2; const float* b2;
@@ -301,6 +311,29 @@ int srn_hifigan_resunit_route(const SrnResUnitParams* p, int32_t out[3]);
  * are device data and cannot steer the route; the argument may be NULL). */
 int srn_hifigan_resunit_ragged(const SrnResUnitParams* p, const int32_t* lens, void* stream);
 int srn_hifigan_resunit_ragged_route(const SrnResUnitParams* p, const int32_t* lens_or_null, int32_t out[3]);
+/* The residual unit of a causal generator (HiFiGANResidualBlock with use_causal_conv, residual_block.py:195-258 over
+ * vocoder/layers/causal_conv.py:11-41): both convs are left-padded with zeros,
+ *     xt = CausalConv_k,dil(LeakyReLU(x));  xt = CausalConv_k,1(LeakyReLU(xt));  y = xt + x   [+ res2] [/ post_div].
+ * The same params struct, read differently in one place: p->x points at (n_batch, H + T, C) rows per item, with
+ * H = (k - 1) (dilation + 1) -- H history rows followed by the T rows of this call -- items x_bs apart.  out and res2
+ * are (n_batch, T, C) as in the dense unit; the residual x of output row t is input row H + t; res2, post_div and the
+ * out / res2 aliasing rule are the dense unit's.
+ * `lead`: device array of n_batch int32; with v_b = clamp(lead[b], 0, H), item b is computed as the unit applied to an
+ * utterance that starts v_b rows before this call's first row:
+ *   - input rows before H - v_b are never read as data (they may hold anything, NaN included) and count as zeros;
+ *   - intermediate rows that lie before that utterance's row 0 are zero -- the second conv's causal padding -- and not
+ *     conv1(0) + b1;
+ *   - v_b = 0 is the one-shot causal unit on T rows, v_b = H any call in mid-stream: the left edge is data, as the
+ *     right edge is in the ragged call, so one prebuilt call (and one captured graph) serves every chunk of a stream.
+ * Forms: the two exact-fp32 ones -- resunit_f32.hip's, and the shared one under SRN_RESUNIT_ROUTE_SHARED (or where the
+ * fp32 form is not eligible: slope outside [0, 1], an item of 2^31 bytes) -- each the CAUSAL instance of the one kernel
+ * text its dense unit runs: the same tile grid, the same number of staged rows (all of them on the left), the same LDS.
+ * There is no split-bf16 variant: SRN_PREC_BF16X3 and SRN_PREC_BF16X6 run the exact-fp32 form (w1_hi / w2_hi are not
+ * read).  Validation as the dense call (C 32 or 64, k odd, (k - 1) dilation <= 50, alignment of x); a NULL `lead` is a
+ * validation error, nothing is launched.  srn_hifigan_resunit_causal_route reports {form, output tiles per item,
+ * workgroups} like srn_hifigan_resunit_route (the leads are device data; the argument may be NULL). */
+int srn_hifigan_resunit_causal(const SrnResUnitParams* p, const int32_t* lead, void* stream);
+int srn_hifigan_resunit_causal_route(const SrnResUnitParams* p, const int32_t* lead_or_null, int32_t out[3]);
 
 /* SiFiGAN pitch-dependent dilated-conv operand gather (row a9; un-vendored `sifigan` package, parity unpinned):
  * out (B, T, 3C) = [lrelu(x[t]) | lrelu(x[t - r]) | lrelu(x[t + r])], r = rint(d[b, t] * dilation), zero outside. */
@@ -336,6 +369,11 @@ int srn_gru_recur_last_ragged(const float* gi, const float* w_hh_t, const float*
  * int32, each >= 0).  NULL pointers, non-positive sizes and items that overlap (bs < rows_cap * n_cols with B > 1) are
  * refused. */
 int srn_zero_rows_ragged(float* x, int64_t bs, int n_cols, const int32_t* n_rows, int B, int rows_cap, void* stream);
+/* The ReplicationPad1d((1, 0)) in front of a CausalConvTranspose1d (vocoder/layers/causal_conv.py:44-77), keyed on
+ * device data: where lead[b] <= 0 (item b's stream has not begun), row 0 of x + b * bs becomes a copy of its row 1, rows
+ * of n_cols contiguous floats back to back; where lead[b] > 0 the item is not touched (row 0 holds the last row of the
+ * chunk before).  lead: device, B int32.  NULL pointers, non-positive sizes and overlapping items are refused. */
+int srn_replicate_first_row(float* x, int64_t bs, int n_cols, const int32_t* lead, int B, void* stream);
 
 /* StyleTokenLayer (style_encoder.py:235-252 + gst/attention.py:110-184,298-300): ref (B, Dq) -> out (B, F), with its
  * input-independent parts formed at weight-packing time: k, v (n_tok, F) = tanh(embs) W_k^T + b_k / W_v^T + b_v;

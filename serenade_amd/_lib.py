@@ -122,6 +122,8 @@ _SIGS = {
     "srn_hifigan_resunit_route": (c_int, [POINTER(SrnResUnitParams), POINTER(c_int32)]),
     "srn_hifigan_resunit_ragged": (c_int, [POINTER(SrnResUnitParams), _P, _P]),
     "srn_hifigan_resunit_ragged_route": (c_int, [POINTER(SrnResUnitParams), _P, POINTER(c_int32)]),
+    "srn_hifigan_resunit_causal": (c_int, [POINTER(SrnResUnitParams), _P, _P]),
+    "srn_hifigan_resunit_causal_route": (c_int, [POINTER(SrnResUnitParams), _P, POINTER(c_int32)]),
     "srn_gn_mish_apply": (c_int, [_P, _P, _P, _P, _P, c_int64, _P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
     "srn_resblock_tail": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int,
                                   c_float, c_float, c_int, _P]),
@@ -139,6 +141,7 @@ _SIGS = {
     "srn_renorm": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int, _P]),
     "srn_out_conv_tanh": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
     "srn_out_conv_tanh_ragged": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
+    "srn_out_conv_tanh_causal": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
     "srn_pd_gather": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_float, _P]),
     "srn_pd_gather_ragged": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, _P]),
     "srn_pad_signal": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
@@ -150,6 +153,7 @@ _SIGS = {
     "srn_gru_recur_last": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "srn_gru_recur_last_ragged": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "srn_zero_rows_ragged": (c_int, [_P, c_int64, c_int, _P, c_int, c_int, _P]),
+    "srn_replicate_first_row": (c_int, [_P, c_int64, c_int, _P, c_int, _P]),
     "srn_style_token_attention_kv": (c_int, [_P] * 8 + [c_int] * 5 + [_P]),
     "srn_rowln_fwd": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int, c_float, _P]),
     "srn_rowln_bwd": (c_int, [_P, _P, _P, c_int64, _P, _P, c_int, c_int, c_int, c_float, _P]),

@@ -163,11 +163,15 @@ def hifigan_shapes(in_channels=80, out_channels=1, channels=512, kernel_size=7,
                    upsample_scales=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4),
                    resblock_kernel_sizes=(3, 7, 11),
                    resblock_dilations=((1, 3, 5), (1, 3, 5), (1, 3, 5)),
-                   use_additional_convs=True, weight_norm=True, **_):
+                   use_additional_convs=True, weight_norm=True, causal=False, use_causal_conv=None, **_):
+    """causal (or the reference's own keyword, use_causal_conv): the generator is built from CausalConv1d /
+    CausalConvTranspose1d (vocoder/layers/causal_conv.py), whose convs sit one module deeper (`.conv`, `.deconv`)"""
+    causal = bool(causal if use_causal_conv is None else use_causal_conv)
+    conv, deconv = (".conv", ".deconv") if causal else ("", "")
     d = OrderedDict()
-    _conv(d, "input_conv", channels, in_channels, kernel_size, weight_norm)
+    _conv(d, "input_conv" + conv, channels, in_channels, kernel_size, weight_norm)
     for i, k in enumerate(upsample_kernel_sizes):
-        _conv(d, f"upsamples.{i}.1", channels // 2 ** (i + 1), channels // 2 ** i, k, weight_norm,
+        _conv(d, f"upsamples.{i}.1" + deconv, channels // 2 ** (i + 1), channels // 2 ** i, k, weight_norm,
               transpose=True)
     nb = len(resblock_kernel_sizes)
     for i in range(len(upsample_kernel_sizes)):
@@ -175,11 +179,11 @@ def hifigan_shapes(in_channels=80, out_channels=1, channels=512, kernel_size=7,
         for j in range(nb):
             p = f"blocks.{i * nb + j}"
             for idx in range(len(resblock_dilations[j])):
-                _conv(d, f"{p}.convs1.{idx}.1", c, c, resblock_kernel_sizes[j], weight_norm)
+                _conv(d, f"{p}.convs1.{idx}.1" + conv, c, c, resblock_kernel_sizes[j], weight_norm)
             if use_additional_convs:
                 for idx in range(len(resblock_dilations[j])):
-                    _conv(d, f"{p}.convs2.{idx}.1", c, c, resblock_kernel_sizes[j], weight_norm)
-    _conv(d, "output_conv.1", out_channels, channels // 2 ** len(upsample_kernel_sizes), kernel_size,
+                    _conv(d, f"{p}.convs2.{idx}.1" + conv, c, c, resblock_kernel_sizes[j], weight_norm)
+    _conv(d, "output_conv.1" + conv, out_channels, channels // 2 ** len(upsample_kernel_sizes), kernel_size,
           weight_norm)
     return d
 

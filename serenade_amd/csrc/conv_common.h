@@ -318,10 +318,19 @@ struct SrnResUnitRoute {
 };
 // intermediate rows per tile, in every form of the kernel
 constexpr int srn_resunit_bmi(const int C) { return C == 32 ? 256 : 128; }
-// resunit_f32.hip: whether that form takes the (validated) call, and its launch (lens: NULL, or the per-item lengths of
-// srn_hifigan_resunit_ragged)
-bool srn_resunit_f32_eligible(const SrnResUnitParams& p, const SrnResUnitRoute& r);
-int srn_resunit_f32_launch(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int32_t* lens, hipStream_t stream);
+// The three instances of the unit's one kernel text (resunit.hip, resunit_f32.hip).  What differs between them is where
+// an item's rows begin and end, nothing else: the staging, the tile walk, the weight pipeline and the MFMA order are
+// stated once.
+//   DENSE   rows [0, T) of x exist; both convs are "same" padded.
+//   RAGGED  rows [0, L_z) exist, L_z = min(lens[z], T) device data (srn_hifigan_resunit_ragged).
+//   CAUSAL  both convs reach back only (srn_hifigan_resunit_causal): x holds H = (k - 1)(dilation + 1) history rows in
+//           front of the call's T rows, rows [-v_z, T) exist, v_z = clamp(lead[z], 0, H) device data.
+enum { SRN_UNIT_DENSE = 0, SRN_UNIT_RAGGED = 1, SRN_UNIT_CAUSAL = 2 };
+// resunit_f32.hip: whether that form takes the (validated) call, and its launch.  mode: SRN_UNIT_*; aux: NULL (dense),
+// the per-item lengths of srn_hifigan_resunit_ragged or the per-item leads of srn_hifigan_resunit_causal
+bool srn_resunit_f32_eligible(const SrnResUnitParams& p, const SrnResUnitRoute& r, int mode);
+int srn_resunit_f32_launch(const SrnResUnitParams& p, const SrnResUnitRoute& r, int mode, const int32_t* aux,
+                           hipStream_t stream);
 
 // lowest tap offset and the span (max - min) of the taps
 inline int srn_tap_span(const SrnConvParams& p, int& lo) {

@@ -56,6 +56,18 @@ __global__ __launch_bounds__(ZR_THREADS) void zero_rows_ragged_kernel(float* __r
   }
 }
 
+// ReplicationPad1d((1, 0)) of a stream's first chunk, keyed on device data: where lead[b] <= 0, row 0 of item b becomes a
+// copy of its row 1 (rows of n_cols contiguous floats, back to back).  Grid (chunks of 256 floats, B); lead[b] is one
+// scalar load, uniform over the workgroup, and an item in mid-stream costs that load only.
+__global__ __launch_bounds__(256) void replicate_first_row_kernel(float* __restrict__ x, int64_t bs, int n_cols,
+                                                                  SrnLens lead) {
+  const int b = blockIdx.y;
+  if (lead[b] > 0) return;  // uniform: row 0 holds the previous chunk's last row
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  float* xb = x + (int64_t)b * bs;
+  if (c < n_cols) xb[c] = xb[n_cols + c];
+}
+
 // Style-token attention on PRECOMPUTED keys / values: K = tanh(embs) W_k^T + b_k and V likewise do not depend on the
 // input, so they are formed once at weight-packing time ((n_tok, F) each); the query / output projections read
 // TRANSPOSED weights (wq_t [Dq][F], wo_t [F][F]) so lanes read consecutive addresses.  One workgroup per batch item.
@@ -127,6 +139,17 @@ extern "C" int srn_zero_rows_ragged(float* x, int64_t bs, int n_cols, const int3
   SRN_CHECK_ARG(chunks <= 0x7fffffff, "zero_rows_ragged: too large");
   hipLaunchKernelGGL(zero_rows_ragged_kernel, dim3((unsigned)chunks, B), dim3(ZR_THREADS), 0, (hipStream_t)stream, x,
                      bs, n_cols, n_rows, rows_cap);
+  SRN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int srn_replicate_first_row(float* x, int64_t bs, int n_cols, const int32_t* lead, int B, void* stream) {
+  SRN_CHECK_ARG(x && lead, "replicate_first_row: null");
+  SRN_CHECK_ARG(n_cols > 0 && B > 0 && B <= 65535, "replicate_first_row: bad sizes");
+  SRN_CHECK_ARG(B == 1 || bs >= 2 * (int64_t)n_cols, "replicate_first_row: items of two rows overlap at a batch stride of %lld",
+                (long long)bs);
+  hipLaunchKernelGGL(replicate_first_row_kernel, dim3((unsigned)((n_cols + 255) / 256), B), dim3(256), 0,
+                     (hipStream_t)stream, x, bs, n_cols, lead);
   SRN_CHECK_LAUNCH();
   return 0;
 }

@@ -342,11 +342,15 @@ constexpr int OC_BT = 256;
 // srn_out_conv_tanh_ragged): item b is the dense B = 1 call at T = L_b = min(lens[b], T) -- the same rows staged, the
 // same fmaf chain -- and y[b, L_b .. T) = 0.  L_b is one uniform scalar load per workgroup; input rows >= L_b are not
 // read, and a tile wholly past the item's end only writes its zeros.
-template <int K, int CC, bool RAGGED = false, class... Lens>
+// A third instance, causal (MODE = SRN_UNIT_CAUSAL, no trailing argument; srn_out_conv_tanh_causal): the conv reaches
+// back only and an item of x is (K - 1) history rows followed by its T rows, so output t reads the item's rows
+// t .. t + K - 1 -- the same staging and the same fmaf chain over a window that begins K - 1 rows before the output.
+template <int K, int CC, int MODE = SRN_UNIT_DENSE, class... Lens>
 __global__ __launch_bounds__(256) void out_conv_tanh_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ bias, float* __restrict__ y,
                                                             int T, float slope, const Lens... lens) {
-  static_assert(sizeof...(Lens) == (RAGGED ? 1 : 0), "the ragged instance takes the lengths, the dense one nothing");
+  constexpr bool RAGGED = MODE == SRN_UNIT_RAGGED, CAUSAL = MODE == SRN_UNIT_CAUSAL;
+  static_assert(sizeof...(Lens) == (RAGGED ? 1 : 0), "the ragged instance takes the lengths, the others nothing");
   constexpr int PITCH = CC + 4;  // floats
   constexpr int ROWS = OC_BT + K - 1;
   __shared__ __attribute__((aligned(16))) float sx[ROWS * PITCH];
@@ -361,12 +365,13 @@ __global__ __launch_bounds__(256) void out_conv_tanh_kernel(const float* __restr
       return;
     }
   }
-  const float* xb = x + (int64_t)b * T * CC;
+  if constexpr (CAUSAL) L = T + K - 1;  // the item's rows, history included
+  const float* xb = x + (int64_t)b * (CAUSAL ? T + K - 1 : T) * CC;
   for (int i = threadIdx.x; i < K * CC; i += 256) sw[i] = w[i];
   constexpr int C4 = CC / 4;
   for (int i = threadIdx.x; i < ROWS * C4; i += 256) {
     const int r = i / C4, c4 = i - r * C4;
-    const int ti = t0 + r - (K - 1) / 2;
+    const int ti = t0 + r - (CAUSAL ? 0 : (K - 1) / 2);
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (ti >= 0 && ti < L) v = leaky4(*reinterpret_cast<const float4*>(xb + (int64_t)ti * CC + c4 * 4), slope);
     *reinterpret_cast<float4*>(sx + r * PITCH + c4 * 4) = v;
@@ -398,11 +403,12 @@ __global__ __launch_bounds__(256) void out_conv_tanh_kernel(const float* __restr
 }
 
 // generic (any C % 4 == 0, k <= 16) fallback of the above
-template <bool RAGGED = false, class... Lens>
+template <int MODE = SRN_UNIT_DENSE, class... Lens>
 __global__ __launch_bounds__(256) void out_conv_tanh_generic(const float* __restrict__ x, const float* __restrict__ w,
                                                              const float* __restrict__ bias, float* __restrict__ y,
                                                              int T, int C, int K, float slope, const Lens... lens) {
-  static_assert(sizeof...(Lens) == (RAGGED ? 1 : 0), "the ragged instance takes the lengths, the dense one nothing");
+  constexpr bool RAGGED = MODE == SRN_UNIT_RAGGED, CAUSAL = MODE == SRN_UNIT_CAUSAL;
+  static_assert(sizeof...(Lens) == (RAGGED ? 1 : 0), "the ragged instance takes the lengths, the others nothing");
   const int b = blockIdx.y;
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= T) return;
@@ -414,10 +420,11 @@ __global__ __launch_bounds__(256) void out_conv_tanh_generic(const float* __rest
       return;
     }
   }
-  const float* xb = x + (int64_t)b * T * C;
+  if constexpr (CAUSAL) L = T + K - 1;  // the item's rows, history included
+  const float* xb = x + (int64_t)b * (CAUSAL ? T + K - 1 : T) * C;
   float acc = bias[0];
   for (int j = 0; j < K; ++j) {
-    const int ti = t + j - (K - 1) / 2;
+    const int ti = t + j - (CAUSAL ? 0 : (K - 1) / 2);
     if (ti < 0 || ti >= L) continue;
     for (int c = 0; c < C; ++c) {
       float v = xb[(int64_t)ti * C + c];
@@ -609,11 +616,27 @@ extern "C" int srn_out_conv_tanh_ragged(const float* x, const float* w, const fl
                 "out_conv_tanh_ragged: bad args");
   dim3 grid((T + 255) / 256, B);
   if (C == 32 && k == 7 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {  // the dense entry point's choice
-    hipLaunchKernelGGL((out_conv_tanh_kernel<7, 32, true, SrnLens>), grid, dim3(256), 0, (hipStream_t)stream, x,
+    hipLaunchKernelGGL((out_conv_tanh_kernel<7, 32, SRN_UNIT_RAGGED, SrnLens>), grid, dim3(256), 0, (hipStream_t)stream, x,
                        w, bias, y, T, slope, lens);
   } else {
-    hipLaunchKernelGGL((out_conv_tanh_generic<true, SrnLens>), grid, dim3(256), 0, (hipStream_t)stream, x, w,
+    hipLaunchKernelGGL((out_conv_tanh_generic<SRN_UNIT_RAGGED, SrnLens>), grid, dim3(256), 0, (hipStream_t)stream, x, w,
                        bias, y, T, C, k, slope, lens);
+  }
+  SRN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int srn_out_conv_tanh_causal(const float* x, const float* w, const float* bias, float* y, int B, int T,
+                                        int C, int k, float slope, void* stream) {
+  SRN_CHECK_ARG(x && w && bias && y && B > 0 && T > 0 && C > 0 && k > 0 && k % 2 == 1 && k <= 16,
+                "out_conv_tanh_causal: bad args");
+  dim3 grid((T + 255) / 256, B);
+  if (C == 32 && k == 7 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {  // the dense entry point's choice
+    hipLaunchKernelGGL((out_conv_tanh_kernel<7, 32, SRN_UNIT_CAUSAL>), grid, dim3(256), 0, (hipStream_t)stream, x, w,
+                       bias, y, T, slope);
+  } else {
+    hipLaunchKernelGGL((out_conv_tanh_generic<SRN_UNIT_CAUSAL>), grid, dim3(256), 0, (hipStream_t)stream, x, w, bias,
+                       y, T, C, k, slope);
   }
   SRN_CHECK_LAUNCH();
   return 0;

@@ -58,10 +58,18 @@ struct RCfg {
 // grid.  L_z is one wave-uniform scalar load per tile (and one for the prefetched tile).  A tile wholly past its item's
 // end is computed and stores nothing: the weight pipeline (wj / wbuf, two stages in flight across tiles) advances as
 // on any other tile.
-template <class R, bool RAGGED = false, class... Lens>
+// A third instance, causal (MODE = SRN_UNIT_CAUSAL, one trailing argument: the per-item leads,
+// srn_hifigan_resunit_causal; exact fp32 only): both convs reach back only, so p2 = k - 1 and p1 = (k - 1) dil -- the
+// dense tile's number of staged rows, all of them at or before the tile's own.  x carries H = p2 + p1 history rows in
+// front of the call's rows; row numbers stay relative to the call's first row, and the item exists on [-v_z, T) with
+// v_z = clamp(lead[z], 0, H): the lower edge is data as the upper one is in the ragged instance (conv_common.h).
+template <class R, int MODE = SRN_UNIT_DENSE, class... Lens>
 __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnResUnitParams p, const int tiles_per_z,
                                                             const int n_tiles, const Lens... lens) {
-  static_assert(sizeof...(Lens) == (RAGGED ? 1 : 0), "the ragged instance takes the lengths, the dense one nothing");
+  constexpr bool RAGGED = MODE == SRN_UNIT_RAGGED, CAUSAL = MODE == SRN_UNIT_CAUSAL;
+  static_assert(sizeof...(Lens) == (MODE == SRN_UNIT_DENSE ? 0 : 1),
+                "the ragged instance takes the lengths, the causal one the leads, the dense one nothing");
+  static_assert(!CAUSAL || R::PREC == 0, "the causal unit runs the exact-fp32 forms");
   constexpr int C = R::C, CH = R::CH, NT = R::NTW, MT = R::MTW, BMI = R::BMI, G = R::G, NTH = R::NTH;
   constexpr bool BF = R::PREC != 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_r[];
@@ -74,7 +82,7 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
   const int li = lane & 31;
   const int lh = lane >> 5;
   const int k = p.k, dil = p.dilation, T = p.T;
-  const int p2 = (k - 1) / 2, p1 = p2 * dil;
+  const int p2 = CAUSAL ? k - 1 : (k - 1) / 2, p1 = p2 * dil;  // rows conv2 / conv1 reach back from an output row
   const int BMo = BMI - (k - 1);         // output rows per tile
   const int hr = BMI + (k - 1) * dil;    // image rows in use
   const int U = k * CH;                  // weight units per conv
@@ -85,6 +93,12 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
     if constexpr (RAGGED) return max(min(__builtin_amdgcn_readfirstlane(srn_first(lens...)[z]), T), 0);
     else return T;
   };
+  // the first row of item z that exists, relative to the call's first row: 0, or minus the causal item's lead
+  auto item_lo = [&](const int z) {
+    if constexpr (CAUSAL) return -max(min(__builtin_amdgcn_readfirstlane(srn_first(lens...)[z]), p2 + p1), 0);
+    else return 0;
+  };
+  const float* const x0 = CAUSAL ? p.x + (int64_t)(p2 + p1) * C : p.x;  // row 0 of item 0: behind the history rows
 
   // ---- weight stages: j in [0, 2 S): conv1's stages then conv2's.  Piece q = tid + 256 i of a stage is 16-B
   //      piece (tid & 7) of weight row n = (tid >> 3) + 32 (i & 1) [C = 64] of unit i >> 1 [C = 64] / i [C = 32]:
@@ -138,16 +152,19 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
   auto load_a = [&](const int tile) {
     const int z = tile / tiles_per_z;
     const int t0 = (tile - z * tiles_per_z) * BMo;
-    const float* xz = p.x + (int64_t)z * p.x_bs + a_f4 * 4;
+    const float* xz = x0 + (int64_t)z * p.x_bs + a_f4 * 4;
     const int ti0 = t0 - p2 - p1 + a_r0;
     const int Tz = item_len(z);
+    const int lo = item_lo(z);
     pa_ok = 0;
 #pragma unroll
     for (int j = 0; j < A_LD; ++j) {
       const int ti = ti0 + RSTEP * j;
-      const bool ok = a_r0 + RSTEP * j < hr && ti >= 0 && ti < Tz;
+      const bool ok = a_r0 + RSTEP * j < hr && ti >= lo && ti < Tz;
       pa_ok |= (ok ? 1u : 0u) << j;
-      pa[j] = *reinterpret_cast<const float4*>(xz + (RAGGED ? max(min(ti, Tz - 1), 0) : min(max(ti, 0), T - 1)) * C);
+      // the address is clamped into the rows that exist: nothing outside them is loaded, whatever `ok` says
+      const int tc = CAUSAL ? max(min(ti, T - 1), lo) : RAGGED ? max(min(ti, Tz - 1), 0) : min(max(ti, 0), T - 1);
+      pa[j] = *reinterpret_cast<const float4*>(xz + tc * C);
     }
   };
   // LDS offset of piece j = a_dst0 + j * RSTEP rows (RSTEP is a multiple of 4: the swizzle key does not change)
@@ -292,6 +309,7 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
     const int z = tile / tiles_per_z;
     const int t0 = (tile - z * tiles_per_z) * BMo;
     const int Tz = item_len(z);
+    const int lo = item_lo(z);
     stage_a();  // the previous tile's conv2 ended on a barrier: nobody reads the image any more
     __syncthreads();
     const int next = tile + gridDim.x;
@@ -300,7 +318,7 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
     // ---- conv1 over the x image
     zero_acc();
     conv_pass(dil);
-    // ---- intermediate = LeakyReLU(conv1 + b1), zero outside [0, T), over the image (every wave passed the last
+    // ---- intermediate = LeakyReLU(conv1 + b1), zero outside [lo, T), over the image (every wave passed the last
     //      stage's barrier, so no conv1 read is pending)
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -320,7 +338,7 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
             const int gi = t0 - p2 + mrow0 + i;
             float v = acc[m][n][4 * gq + i] + bias;
             v = v > 0.f ? v : v * slope;
-            if (gi < 0 || gi >= Tz) v = 0.f;
+            if (gi < lo || gi >= Tz) v = 0.f;
             if constexpr (BF) {
               const __bf16 h = (__bf16)v;
               const __bf16 l = (__bf16)(v - (float)h);
@@ -341,7 +359,7 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
     // ---- epilogue: + b2 + x [+ res2] [/ post_div]; rows [t0, t0 + BMo) and < T.  out never aliases x; res2 may be
     //      out itself (running stage sum): every element is loaded by the lane that later stores it.  The loads of a
     //      row quad are issued together and nothing is preloaded across sub-tiles (register budget)
-    const float* __restrict__ xz = p.x + (int64_t)z * p.x_bs + (int64_t)t0 * C;
+    const float* __restrict__ xz = x0 + (int64_t)z * p.x_bs + (int64_t)t0 * C;
     const float* qz = p.res2 ? p.res2 + (int64_t)z * p.res2_bs + (int64_t)t0 * C : nullptr;  // may alias out
     float* oz = p.out + (int64_t)z * p.out_bs + (int64_t)t0 * C;
     const bool divide = p.post_div != 0.f && p.post_div != 1.f;
@@ -378,29 +396,40 @@ __global__ __launch_bounds__(R::NTH, R::NW / 2) void resunit_kernel(const SrnRes
   }
 }
 
-// lens: NULL for the dense call, or the ragged call's per-item lengths (device, n_batch int32)
-template <class R>
-int launch_resunit(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int32_t* lens, hipStream_t stream) {
-  static_assert(R::BMI == srn_resunit_bmi(R::C), "the route's tile height is the kernel's");
-  if (lens) {
-    static SrnSmemAttr smem_attr_ragged;
-    if (const int e = smem_attr_ragged.ensure(reinterpret_cast<const void*>(&resunit_kernel<R, true, SrnLens>),
-                                              R::SMEM))
-      return e;
-    hipLaunchKernelGGL((resunit_kernel<R, true, SrnLens>), dim3(r.grid), dim3(R::NTH), R::SMEM, stream, p, r.tiles_per_z,
-                       r.n_tiles, lens);
-  } else {
-    static SrnSmemAttr smem_attr;
+// one instance's launch: the dense one takes no trailing argument
+template <class R, int MODE>
+int launch_instance(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int32_t* aux, hipStream_t stream) {
+  static SrnSmemAttr smem_attr;  // one per instance
+  if constexpr (MODE == SRN_UNIT_DENSE) {
     if (const int e = smem_attr.ensure(reinterpret_cast<const void*>(&resunit_kernel<R>), R::SMEM)) return e;
     hipLaunchKernelGGL((resunit_kernel<R>), dim3(r.grid), dim3(R::NTH), R::SMEM, stream, p, r.tiles_per_z, r.n_tiles);
+  } else {
+    if (const int e = smem_attr.ensure(reinterpret_cast<const void*>(&resunit_kernel<R, MODE, SrnLens>), R::SMEM))
+      return e;
+    hipLaunchKernelGGL((resunit_kernel<R, MODE, SrnLens>), dim3(r.grid), dim3(R::NTH), R::SMEM, stream, p,
+                       r.tiles_per_z, r.n_tiles, aux);
   }
   SRN_CHECK_LAUNCH();
   return 0;
 }
 
+// mode: SRN_UNIT_*; aux: NULL for the dense call, the ragged call's per-item lengths or the causal call's per-item leads
+// (device, n_batch int32).  The causal instance exists in exact fp32 only (resunit_route never sends it elsewhere).
+template <class R>
+int launch_resunit(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int mode, const int32_t* aux,
+                   hipStream_t stream) {
+  static_assert(R::BMI == srn_resunit_bmi(R::C), "the route's tile height is the kernel's");
+  if constexpr (R::PREC == 0) {
+    if (mode == SRN_UNIT_CAUSAL) return launch_instance<R, SRN_UNIT_CAUSAL>(p, r, aux, stream);
+  }
+  if (mode == SRN_UNIT_RAGGED) return launch_instance<R, SRN_UNIT_RAGGED>(p, r, aux, stream);
+  return launch_instance<R, SRN_UNIT_DENSE>(p, r, nullptr, stream);
+}
+
 // Validation and the choice of the implementation, stated once: srn_hifigan_resunit launches what this answers and
-// srn_hifigan_resunit_route reports it.
-int resunit_route(const SrnResUnitParams* pp, SrnResUnitRoute& r) {
+// srn_hifigan_resunit_route reports it.  mode: SRN_UNIT_DENSE for the dense and the ragged call (whose lengths are data
+// and cannot steer the route), SRN_UNIT_CAUSAL for srn_hifigan_resunit_causal.
+int resunit_route(const SrnResUnitParams* pp, SrnResUnitRoute& r, const int mode = SRN_UNIT_DENSE) {
   SRN_CHECK_ARG(pp != nullptr, "resunit: null params");
   const SrnResUnitParams& p = *pp;
   SRN_CHECK_ARG(p.x && p.w1 && p.b1 && p.w2 && p.b2 && p.out, "resunit: null pointer");
@@ -421,15 +450,15 @@ int resunit_route(const SrnResUnitParams* pp, SrnResUnitRoute& r) {
   SRN_CHECK_ARG(n_tiles > 0 && n_tiles < (1ll << 31), "resunit: bad tile count %lld", (long long)n_tiles);
   r.n_tiles = (int)n_tiles;
   r.grid = (int)(n_tiles < 512 ? n_tiles : 512);  // persistent: two workgroups per CU
-  if (p.precision == SRN_PREC_BF16X3) {
+  if (p.precision == SRN_PREC_BF16X3 && mode != SRN_UNIT_CAUSAL) {
     SRN_CHECK_ARG(p.w1_hi && p.w2_hi, "resunit: split-bf16 mode needs the weight planes w1_hi / w2_hi");
     r.form = SRN_RESUNIT_FORM_BF16X3;
   } else {
     // exact fp32: resunit_f32.hip's form of this kernel (same results bit for bit, ~no vector-ALU work beside the fp32
     // MFMAs) where it is eligible; route SRN_RESUNIT_ROUTE_SHARED keeps this file's instantiation (A-B timing,
-    // bit-identity test)
-    r.form = p.route != SRN_RESUNIT_ROUTE_SHARED && srn_resunit_f32_eligible(p, r) ? SRN_RESUNIT_FORM_F32
-                                                                                   : SRN_RESUNIT_FORM_SHARED_F32;
+    // bit-identity test).  The causal unit has no split-bf16 variant: every precision runs it in exact fp32
+    r.form = p.route != SRN_RESUNIT_ROUTE_SHARED && srn_resunit_f32_eligible(p, r, mode) ? SRN_RESUNIT_FORM_F32
+                                                                                         : SRN_RESUNIT_FORM_SHARED_F32;
   }
   return 0;
 }
@@ -448,18 +477,21 @@ extern "C" int srn_hifigan_resunit_route(const SrnResUnitParams* pp, int32_t out
 
 namespace {
 
-// the launch of a routed call: `lens` NULL (srn_hifigan_resunit) or the per-item lengths (srn_hifigan_resunit_ragged)
-int resunit_launch(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int32_t* lens, hipStream_t stream) {
+// the launch of a routed call: `aux` NULL (srn_hifigan_resunit), the per-item lengths (srn_hifigan_resunit_ragged) or
+// the per-item leads (srn_hifigan_resunit_causal)
+int resunit_launch(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int mode, const int32_t* aux,
+                   hipStream_t stream) {
   switch (r.form) {
     case SRN_RESUNIT_FORM_BF16X3:
-      return p.C == 32 ? launch_resunit<RCfg<32, 1>>(p, r, lens, stream) : launch_resunit<RCfg<64, 1>>(p, r, lens, stream);
+      return p.C == 32 ? launch_resunit<RCfg<32, 1>>(p, r, mode, aux, stream)
+                       : launch_resunit<RCfg<64, 1>>(p, r, mode, aux, stream);
     case SRN_RESUNIT_FORM_F32:
-      return srn_resunit_f32_launch(p, r, lens, stream);
+      return srn_resunit_f32_launch(p, r, mode, aux, stream);
     default:
       // eight waves per workgroup (A/B on the B = 8 x T = 1024 vocoder, 4 -> 8 waves: k 3 units 0.62 -> 0.51 ms,
       // k 7 1.17 -> 1.05, k 11 1.74 -> 1.61 at C = 64; all 18 units 16.7 -> 14.9 ms)
-      return p.C == 32 ? launch_resunit<RCfg<32, 0, 8>>(p, r, lens, stream)
-                       : launch_resunit<RCfg<64, 0, 8>>(p, r, lens, stream);
+      return p.C == 32 ? launch_resunit<RCfg<32, 0, 8>>(p, r, mode, aux, stream)
+                       : launch_resunit<RCfg<64, 0, 8>>(p, r, mode, aux, stream);
   }
 }
 
@@ -468,7 +500,7 @@ int resunit_launch(const SrnResUnitParams& p, const SrnResUnitRoute& r, const in
 extern "C" int srn_hifigan_resunit(const SrnResUnitParams* pp, void* stream_) {
   SrnResUnitRoute r;
   if (const int e = resunit_route(pp, r)) return e;
-  return resunit_launch(*pp, r, nullptr, reinterpret_cast<hipStream_t>(stream_));
+  return resunit_launch(*pp, r, SRN_UNIT_DENSE, nullptr, reinterpret_cast<hipStream_t>(stream_));
 }
 
 // The ragged call: the dense call's validation and route (resunit_route, stated once: T sizes the tile grid whatever
@@ -482,5 +514,25 @@ extern "C" int srn_hifigan_resunit_ragged(const SrnResUnitParams* pp, const int3
   SrnResUnitRoute r;
   if (const int e = resunit_route(pp, r)) return e;
   SRN_CHECK_ARG(lens != nullptr, "resunit_ragged: null lens");
-  return resunit_launch(*pp, r, lens, reinterpret_cast<hipStream_t>(stream_));
+  return resunit_launch(*pp, r, SRN_UNIT_RAGGED, lens, reinterpret_cast<hipStream_t>(stream_));
+}
+
+// The causal call: the dense call's validation and tile grid (the same rows per tile, all of them staged on the left),
+// the exact-fp32 forms only, then that form's CAUSAL instantiation.
+extern "C" int srn_hifigan_resunit_causal_route(const SrnResUnitParams* pp, const int32_t* lead_or_null, int32_t out[3]) {
+  (void)lead_or_null;  // device data: the route cannot depend on it
+  SRN_CHECK_ARG(out != nullptr, "resunit_causal_route: null out");
+  SrnResUnitRoute r;
+  if (const int e = resunit_route(pp, r, SRN_UNIT_CAUSAL)) return e;
+  out[0] = r.form;
+  out[1] = r.tiles_per_z;
+  out[2] = r.grid;
+  return 0;
+}
+
+extern "C" int srn_hifigan_resunit_causal(const SrnResUnitParams* pp, const int32_t* lead, void* stream_) {
+  SrnResUnitRoute r;
+  if (const int e = resunit_route(pp, r, SRN_UNIT_CAUSAL)) return e;
+  SRN_CHECK_ARG(lead != nullptr, "resunit_causal: null lead");
+  return resunit_launch(*pp, r, SRN_UNIT_CAUSAL, lead, reinterpret_cast<hipStream_t>(stream_));
 }

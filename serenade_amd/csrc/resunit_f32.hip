@@ -41,17 +41,27 @@ struct UCfg {
   static_assert(G * C * 8 == NTH, "one 16-B weight piece per thread per stage");
 };
 
-// One kernel text, two instances.  Dense (RAGGED = false, no `lens` argument: the kernel's arguments and code are what
-// they were before the ragged entry point existed -- item_len() folds to T).  Ragged (RAGGED = true, one trailing
-// argument: the per-item lengths): item z is computed as the dense call with n_batch = 1, T = L_z = min(lens[z], T)
-// computes it -- L_z takes T's place in the receptive field's descriptor, the intermediate mask and row_end, while T
-// still sizes the tile grid.  L_z is one wave-uniform scalar load per tile (and one for the prefetched tile); nothing
-// per element.  A tile that lies wholly past its item's end is computed and stores nothing (row_end <= 0): the weight
-// pipeline (wj / wbuf, two stages in flight across tiles) advances exactly as on any other tile.
-template <class R, bool RAGGED = false, class... Lens>
+// One kernel text, three instances (conv_common.h, SRN_UNIT_*).  Dense (no `lens` argument: the kernel's arguments
+// and code are what they were before the other entry points existed -- item_len() folds to T, item_lo() to 0).  Ragged
+// (one trailing argument: the per-item lengths): item z is computed as the dense call with n_batch = 1,
+// T = L_z = min(lens[z], T) computes it -- L_z takes T's place in the receptive field's descriptor, the intermediate
+// mask and row_end, while T still sizes the tile grid.  L_z is one wave-uniform scalar load per tile (and one for the
+// prefetched tile); nothing per element.  A tile that lies wholly past its item's end is computed and stores nothing
+// (row_end <= 0): the weight pipeline (wj / wbuf, two stages in flight across tiles) advances exactly as on any other
+// tile.
+// Causal (one trailing argument: the per-item leads, srn_hifigan_resunit_causal): both convs reach back only, so the
+// rows a tile stages are the dense tile's count, all of them at or before the tile's own rows: p2 = k - 1 rows for
+// conv2 and p1 = (k - 1) dil for conv1 where the dense unit has half of each on either side.  x carries H = p2 + p1
+// history rows in front of the call's rows, and row numbers stay relative to the call's first row: the item exists on
+// [-v_z, T) with v_z = clamp(lead[z], 0, H) -- the lower edge is data as the upper one is in the ragged instance.  The
+// receptive field's descriptor begins at row -v_z, so everything before it reads as zeros whatever it holds, and the
+// intermediate is zero before -v_z.
+template <class R, int MODE = SRN_UNIT_DENSE, class... Lens>
 __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitParams p, const int tiles_per_z,
                                                              const int n_tiles, const FDiv d_tpz, const Lens... lens) {
-  static_assert(sizeof...(Lens) == (RAGGED ? 1 : 0), "the ragged instance takes the lengths, the dense one nothing");
+  constexpr bool RAGGED = MODE == SRN_UNIT_RAGGED, CAUSAL = MODE == SRN_UNIT_CAUSAL;
+  static_assert(sizeof...(Lens) == (MODE == SRN_UNIT_DENSE ? 0 : 1),
+                "the ragged instance takes the lengths, the causal one the leads, the dense one nothing");
   constexpr int C = R::C, CH = R::CH, BMI = R::BMI, G = R::G;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_u[];
   unsigned char* const sA = smem_u;
@@ -63,7 +73,7 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
   const int li = lane & 31;
   const int lh = lane >> 5;
   const int k = p.k, dil = p.dilation, T = p.T;
-  const int p2 = (k - 1) / 2, p1 = p2 * dil;
+  const int p2 = CAUSAL ? k - 1 : (k - 1) / 2, p1 = p2 * dil;  // rows conv2 / conv1 reach back from an output row
   const int BMo = BMI - (k - 1);       // output rows per tile
   const int hr = BMI + (k - 1) * dil;  // image rows in use
   const int U = k * CH;                // weight units per conv
@@ -74,6 +84,12 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
     if constexpr (RAGGED) return max(min(__builtin_amdgcn_readfirstlane(srn_first(lens...)[z]), T), 0);
     else return T;
   };
+  // the first row of item z that exists, relative to the call's first row: 0, or minus the causal item's lead
+  auto item_lo = [&](const int z) {
+    if constexpr (CAUSAL) return -max(min(__builtin_amdgcn_readfirstlane(srn_first(lens...)[z]), p2 + p1), 0);
+    else return 0;
+  };
+  const float* const x0 = CAUSAL ? p.x + (int64_t)(p2 + p1) * C : p.x;  // row 0 of item 0: behind the history rows
 
   // ---- weight stages j in [0, 2 S): conv1's then conv2's.  This thread's piece: 16-B piece (tid & 7) of weight row n
   //      of unit u0 + g of the stage -- row and piece in the per-lane offset, the unit in the scalar offset
@@ -103,8 +119,9 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
   auto load_a = [&](const int tile) {
     const int z = fdiv(tile, d_tpz);
     const int t0 = (tile - z * tiles_per_z) * BMo;
-    const __amdgpu_buffer_rsrc_t rs_x = srn_buffer_rsrc(p.x + (int64_t)z * p.x_bs, item_len(z) * C * 4);
-    const int v0 = a_voff + (t0 - p2 - p1) * (C * 4);  // negative rows wrap to offsets >= 2^31: out of range, zeros
+    const int lo = item_lo(z);
+    const __amdgpu_buffer_rsrc_t rs_x = srn_buffer_rsrc(x0 + (int64_t)z * p.x_bs + lo * C, (item_len(z) - lo) * C * 4);
+    const int v0 = a_voff + (t0 - p2 - p1 - lo) * (C * 4);  // rows before `lo` wrap to offsets >= 2^31: out of range, zeros
 #pragma unroll
     for (int j = 0; j < A_LD; ++j) pa[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, v0 + j * (RSTEP * C * 4), 0, 0);
   };
@@ -188,6 +205,7 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
     const int z = fdiv(tile, d_tpz);
     const int t0 = (tile - z * tiles_per_z) * BMo;
     const int Tz = item_len(z);
+    const int lo = item_lo(z);
     stage_a();  // the previous tile's conv2 ended on a barrier: nobody reads the image any more
     __syncthreads();
     const int next = tile + gridDim.x;
@@ -196,9 +214,9 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
     // ---- conv1 over the x image
     zero_acc();
     conv_pass(dil);
-    // ---- intermediate = LeakyReLU(conv1 + b1), zero outside [0, T), over the image (every wave passed the last
+    // ---- intermediate = LeakyReLU(conv1 + b1), zero outside [lo, T), over the image (every wave passed the last
     //      stage's barrier, so no conv1 read is pending)
-    if (t0 - p2 >= 0 && t0 - p2 + BMI <= Tz) {
+    if (t0 - p2 >= lo && t0 - p2 + BMI <= Tz) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float v = acc[r] + bias1;
@@ -211,7 +229,7 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
         const int gi = t0 - p2 + wm0 + 4 * lh + dr;
         float v = acc[r] + bias1;
         v = fmaxf(v, v * slope);
-        if (gi < 0 || gi >= Tz) v = 0.f;
+        if (gi < lo || gi >= Tz) v = 0.f;
         *reinterpret_cast<float*>(sA + mid_lane + dr * 144) = v;
       }
     }
@@ -226,7 +244,7 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
     const int row_end = RAGGED ? max(min(BMo, Tz - t0), 0) : min(BMo, T - t0);
     const int64_t zoff = (int64_t)t0 * C;
     const int io_bytes = row_end * C * 4;  // the tile's rows that exist: anything past them is out of range
-    const __amdgpu_buffer_rsrc_t rs_xe = srn_buffer_rsrc(p.x + (int64_t)z * p.x_bs + zoff, io_bytes);
+    const __amdgpu_buffer_rsrc_t rs_xe = srn_buffer_rsrc(x0 + (int64_t)z * p.x_bs + zoff, io_bytes);
     const __amdgpu_buffer_rsrc_t rs_qe =
         srn_buffer_rsrc(has_q ? p.res2 + (int64_t)z * p.res2_bs + zoff : p.x, has_q ? io_bytes : 0);
     const __amdgpu_buffer_rsrc_t rs_oe = srn_buffer_rsrc(p.out + (int64_t)z * p.out_bs + zoff, io_bytes);
@@ -268,37 +286,47 @@ __global__ __launch_bounds__(NTH, 4) void resunit_f32_kernel(const SrnResUnitPar
   }
 }
 
-template <class R>
-int launch_unit(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int32_t* lens, hipStream_t stream) {
-  static_assert(R::BMI == srn_resunit_bmi(R::C), "the route's tile height is the kernel's");
-  if (lens) {
-    static SrnSmemAttr smem_attr_ragged;
-    if (const int e = smem_attr_ragged.ensure(reinterpret_cast<const void*>(&resunit_f32_kernel<R, true, SrnLens>),
-                                              R::SMEM))
-      return e;
-    hipLaunchKernelGGL((resunit_f32_kernel<R, true, SrnLens>), dim3(r.grid), dim3(NTH), R::SMEM, stream, p, r.tiles_per_z,
-                       r.n_tiles, make_fdiv((uint32_t)r.tiles_per_z), lens);
-  } else {
-    static SrnSmemAttr smem_attr;
+// one instance's launch: the dense one takes no trailing argument
+template <class R, int MODE>
+int launch_instance(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int32_t* aux, hipStream_t stream) {
+  static SrnSmemAttr smem_attr;  // one per instance
+  if constexpr (MODE == SRN_UNIT_DENSE) {
     if (const int e = smem_attr.ensure(reinterpret_cast<const void*>(&resunit_f32_kernel<R>), R::SMEM)) return e;
     hipLaunchKernelGGL((resunit_f32_kernel<R>), dim3(r.grid), dim3(NTH), R::SMEM, stream, p, r.tiles_per_z, r.n_tiles,
                        make_fdiv((uint32_t)r.tiles_per_z));
+  } else {
+    if (const int e = smem_attr.ensure(reinterpret_cast<const void*>(&resunit_f32_kernel<R, MODE, SrnLens>), R::SMEM))
+      return e;
+    hipLaunchKernelGGL((resunit_f32_kernel<R, MODE, SrnLens>), dim3(r.grid), dim3(NTH), R::SMEM, stream, p, r.tiles_per_z,
+                       r.n_tiles, make_fdiv((uint32_t)r.tiles_per_z), aux);
   }
   SRN_CHECK_LAUNCH();
   return 0;
+}
+
+template <class R>
+int launch_unit(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int mode, const int32_t* aux,
+                hipStream_t stream) {
+  static_assert(R::BMI == srn_resunit_bmi(R::C), "the route's tile height is the kernel's");
+  if (mode == SRN_UNIT_CAUSAL) return launch_instance<R, SRN_UNIT_CAUSAL>(p, r, aux, stream);
+  if (mode == SRN_UNIT_RAGGED) return launch_instance<R, SRN_UNIT_RAGGED>(p, r, aux, stream);
+  return launch_instance<R, SRN_UNIT_DENSE>(p, r, nullptr, stream);
 }
 
 }  // namespace
 
 // Whether this form takes the call; otherwise the caller runs resunit.hip's fp32 form.  `p` has been validated and `r`
 // holds its tile counts (resunit.hip's resunit_route).
-bool srn_resunit_f32_eligible(const SrnResUnitParams& p, const SrnResUnitRoute& r) {
+bool srn_resunit_f32_eligible(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int mode) {
   if (!(p.slope >= 0.f && p.slope <= 1.f)) return false;           // LeakyReLU as max(x, slope x)
-  if ((int64_t)p.T * p.C * 4 >= 0x7fffffffll) return false;        // 32-bit byte offsets inside one item
+  const int hist = mode == SRN_UNIT_CAUSAL ? (p.k - 1) * (p.dilation + 1) : 0;  // the causal item's rows in front
+  if (((int64_t)p.T + hist) * p.C * 4 >= 0x7fffffffll) return false;  // 32-bit byte offsets inside one item
   return r.n_tiles < (1 << 26);                                    // fdiv's range
 }
 
-// lens: NULL for the dense call, or the ragged call's per-item lengths (device, n_batch int32)
-int srn_resunit_f32_launch(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int32_t* lens, hipStream_t stream) {
-  return p.C == 32 ? launch_unit<UCfg<32>>(p, r, lens, stream) : launch_unit<UCfg<64>>(p, r, lens, stream);
+// aux: NULL for the dense call, the ragged call's per-item lengths or the causal call's per-item leads (device, n_batch
+// int32)
+int srn_resunit_f32_launch(const SrnResUnitParams& p, const SrnResUnitRoute& r, const int mode, const int32_t* aux,
+                           hipStream_t stream) {
+  return p.C == 32 ? launch_unit<UCfg<32>>(p, r, mode, aux, stream) : launch_unit<UCfg<64>>(p, r, mode, aux, stream);
 }

@@ -157,25 +157,33 @@ def _item_lens(lens, n_batch, what):
 class ResUnitOp(_StructOp):
     """A prebuilt srn_hifigan_resunit call: one fused HiFi-GAN residual unit (see include/serenade_hip.h).  With `lens`
     (_item_lens) it is a srn_hifigan_resunit_ragged call of the same struct: item b is computed as its own n_batch = 1,
-    T = lens[b] dense call; rows at or past lens[b] are neither read nor written."""
+    T = lens[b] dense call; rows at or past lens[b] are neither read nor written.  With `lead` (_item_lens) it is a
+    srn_hifigan_resunit_causal call: both convs reach back only, `x` holds (k - 1) (dilation + 1) history rows in front
+    of each item's T rows, and item b's utterance began clamp(lead[b], 0, history) rows before this call's first."""
 
     __slots__ = ("_wplanes",)
     _profiled = True  # timed with the other contraction launches
 
-    def __init__(self, lens=None, **kw):
-        if lens is None:
+    def __init__(self, lens=None, lead=None, **kw):
+        if lens is None and lead is None:
             super().__init__("srn_hifigan_resunit", kw)
             return
-        super().__init__("srn_hifigan_resunit_ragged", dict(kw, lens=_item_lens(lens, kw["n_batch"], "ResUnitOp")))
-        entry, lens_p = self._fn, ctypes.c_void_p(_ptr(lens))
-        self._fn = lambda p, stream: entry(p, lens_p, stream)
+        if lead is not None:
+            if lens is not None:
+                raise TypeError("ResUnitOp: lens and lead exclude each other")
+            super().__init__("srn_hifigan_resunit_causal", dict(kw, lead=_item_lens(lead, kw["n_batch"], "ResUnitOp")))
+        else:
+            super().__init__("srn_hifigan_resunit_ragged", dict(kw, lens=_item_lens(lens, kw["n_batch"], "ResUnitOp")))
+        entry, data_p = self._fn, ctypes.c_void_p(_ptr(lens if lead is None else lead))
+        self._fn = lambda p, stream: entry(p, data_p, stream)
 
     def _fill(self, *, x, w1, b1, w2, b2, out, n_batch, T, C, k, dilation, slope, res2=None, post_div=0.0,
-              precision=None, route=0, x_bs=None, res2_bs=None, out_bs=None, lens=None):
+              precision=None, route=0, x_bs=None, res2_bs=None, out_bs=None, lens=None, lead=None):
         p = SrnResUnitParams()
         p.n_batch, p.T, p.C, p.k, p.dilation, p.slope = int(n_batch), int(T), int(C), int(k), int(dilation), float(slope)
         item = int(T) * int(C)  # batch strides: contiguous items unless given
-        p.x, p.x_bs = _ptr(x), item if x_bs is None else int(x_bs)
+        hist = 0 if lead is None else (int(k) - 1) * (int(dilation) + 1) * int(C)  # the causal item's rows in front
+        p.x, p.x_bs = _ptr(x), item + hist if x_bs is None else int(x_bs)
         p.w1, p.b1, p.w2, p.b2 = _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2)
         p.res2, p.res2_bs = _ptr(res2), item if res2_bs is None else int(res2_bs)
         p.post_div = float(post_div)
@@ -183,7 +191,7 @@ class ResUnitOp(_StructOp):
         p.precision = int(DEFAULT_PRECISION if precision is None else precision)
         p.route = int(route)  # _lib.RESUNIT_ROUTE_SHARED: resunit.hip's exact-fp32 form (testing / A-B timing)
         self._wplanes = None
-        if p.precision == _lib.PREC_BF16X3 and w1.is_cuda:
+        if p.precision == _lib.PREC_BF16X3 and w1.is_cuda and lead is None:  # the causal unit runs exact fp32
             self._wplanes = (weight_planes(w1, C, k, C, k * C), weight_planes(w2, C, k, C, k * C))
             p.w1_hi, p.w2_hi = self._wplanes[0][0].data_ptr(), self._wplanes[1][0].data_ptr()
         return p
@@ -471,6 +479,11 @@ def out_conv_tanh_op(x, w, bias, y, B, T, C, k, slope, lens=None):
     return CallOp("srn_out_conv_tanh_ragged", (x, w, bias, y, lens, B, T, C, k, slope))
 
 
+def out_conv_tanh_causal_op(x, w, bias, y, B, T, C, k, slope):
+    """x (B, (k - 1) + T, C): k - 1 history rows in front of each item's T rows (zeros at the start of an utterance)"""
+    return CallOp("srn_out_conv_tanh_causal", (x, w, bias, y, B, T, C, k, slope))
+
+
 def pd_gather_op(x, d, out, B, T, C, dilation, slope, lens=None):
     """lens (_item_lens): a ragged batch, lens[b] rows of item b; rows past an item's end are neither read nor
     written"""
@@ -495,6 +508,13 @@ def zero_rows_ragged_op(x, bs, n_cols, n_rows, B, rows_cap):
     become zero"""
     n_rows = _item_lens(n_rows, B, "zero_rows_ragged_op")
     return CallOp("srn_zero_rows_ragged", (x, bs, n_cols, n_rows, B, rows_cap))
+
+
+def replicate_first_row_op(x, bs, n_cols, lead, B):
+    """lead (_item_lens): where lead[b] <= 0, row 0 of item b of x (rows of n_cols floats, items bs floats apart) becomes
+    a copy of its row 1 -- ReplicationPad1d((1, 0)) of a stream that has not begun"""
+    lead = _item_lens(lead, B, "replicate_first_row_op")
+    return CallOp("srn_replicate_first_row", (x, bs, n_cols, lead, B))
 
 
 def style_token_attention_kv_op(ref, wq_t, bq, k, v, wo_t, bo, out, B, Dq, n_tok, F, n_head):
@@ -540,6 +560,17 @@ def convtranspose_phases(w, stride, padding):
         packed = torch.stack(mats, dim=1).reshape(co, len(taps) * ci).contiguous()
         phases.append((taps, packed))
     return phases
+
+
+def convtranspose_phases_causal(w, stride):
+    """convtranspose_phases for CausalConvTranspose1d (vocoder/layers/causal_conv.py:44-77): kernel 2 * stride, the
+    input padded by one replicated row on the left, the first and last `stride` outputs cut.  Over a [1 history row |
+    rows] buffer, whose row m + 1 is input row m, output m * stride + r is  W[:, :, r + stride]^T x[m - 1] +
+    W[:, :, r]^T x[m]:  taps (0, 1) of the buffer for every phase."""
+    ci, co, k = w.shape
+    assert k == 2 * stride
+    return [([0, 1], torch.stack([w[:, :, r + stride].t(), w[:, :, r].t()], dim=1).reshape(co, 2 * ci).contiguous())
+            for r in range(stride)]
 
 
 def pack_geglu(w, b):

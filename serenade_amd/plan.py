@@ -68,10 +68,11 @@ def tensors_of(obj):
 # ---------------------------------------------------------------------------------------------- contractions
 def conv_op(B, inp, cin, T_in, w, b, out, cout, T_out, taps, ld_in=None, **kw):
     """Conv1d over a (B, T_in, cin) channels-last batch into (B, T_out, cout): packed weight `w`, bias `b`, input-row
-    offsets `taps`.  ld_in: row length of `inp` when it is wider than cin; out_bs / ld_out override the dense output."""
+    offsets `taps`.  ld_in: row length of `inp` when it is wider than cin; in_bs / out_bs / ld_out override the dense
+    item strides (a window of a longer buffer)."""
     ld_in = cin if ld_in is None else ld_in
     return ConvOp(in0=inp, w=w, out=out, n_batch=B, T_in=T_in, T_out=T_out, C_in=cin, N=cout,
-                  in0_bs=T_in * ld_in, ld_in0=ld_in, ldw=w.shape[1], out_bs=kw.pop("out_bs", T_out * cout),
+                  in0_bs=kw.pop("in_bs", T_in * ld_in), ld_in0=ld_in, ldw=w.shape[1], out_bs=kw.pop("out_bs", T_out * cout),
                   ld_out=kw.pop("ld_out", cout), bias=b, taps=taps, **kw)
 
 
@@ -86,6 +87,11 @@ def linear_op(inp, rows, K, w, b, out, N, **kw):
 # dense plan; a (B,) int32 device tensor makes the length data -- a conv reads rows at or past its input's length as the
 # zeros an item alone would be padded with (len_in), the fused unit runs its ragged entry point.
 FUSED_UNIT_CHANNELS = (32, 64)  # stage widths whose residual units run as one fused launch (srn_hifigan_resunit)
+
+
+def fused_unit(cv, C):
+    """whether the two-conv unit `cv` (packed: k, d, w1, ..., w2) of a C-channel stage runs as one fused launch"""
+    return "w2" in cv and C in FUSED_UNIT_CHANNELS and (cv["k"] - 1) * cv["d"] <= 50 and cv["k"] % 2 == 1
 
 
 def masked(lens, out=False):
@@ -125,7 +131,7 @@ def mrf_stage_ops(ol, B, u, p0, p1, xt, acc, blocks, C, T, slope, lens=None):
                 if j == nb - 1:
                     fin.update(post=ops.POST_DIV, post_div=float(nb))
             skip = dict(res=x, res_mode=ops.RES_ADD, res_bs=T * C, ld_res=C, **fin, **masked(lens))
-            if "w2" in cv and C in FUSED_UNIT_CHANNELS and (cv["k"] - 1) * cv["d"] <= 50 and cv["k"] % 2 == 1:
+            if fused_unit(cv, C):
                 # thin stage: the whole unit in one launch (resunit.hip); stage sum / mean in its epilogue
                 ol.append(ops.ResUnitOp(x=x, w1=cv["w1"], b1=cv["b1"], w2=cv["w2"], b2=cv["b2"], out=dst, n_batch=B,
                                         T=T, C=C, k=cv["k"], dilation=cv["d"], slope=slope, res2=fin.get("res2"),
@@ -142,6 +148,177 @@ def mrf_stage_ops(ol, B, u, p0, p1, xt, acc, blocks, C, T, slope, lens=None):
                 ol.append(conv_op(B, x, C, T, cv["w1"], cv["b1"], dst, C, T, ops.conv_taps(cv["k"], cv["d"]),
                                   pro_act=ops.ACT_LEAKY, pro_slope=slope, **skip))
             x = dst
+
+
+# The same stages of a causal generator (use_causal_conv: CausalConv1d / CausalConvTranspose1d, vocoder/layers/
+# causal_conv.py).  No output row depends on a later input row, so a stage can run chunk by chunk: every conv reads a
+# [history | chunk] buffer of its own -- the last H rows of what it read in the chunk before, then this chunk's rows --
+# as a VALID conv (taps 0, d, 2d, ...), and writes into the chunk rows of its consumer's buffer.  Zero history is the
+# convs' causal zero padding, so ONE op list is the one-shot plan (zero histories, every lead 0, run once) and the
+# streaming plan (the histories carried over after every chunk, HistoryArena.carry_ops).
+class HistBuf:
+    """one [history | chunk] buffer inside a plan's arena: B items of H + T rows of C floats, items `bs` floats apart"""
+
+    __slots__ = ("arena", "off", "B", "H", "T", "C")
+
+    def __init__(self, arena, off, B, H, T, C):
+        self.arena, self.off, self.B, self.H, self.T, self.C = arena, off, B, H, T, C
+
+    @property
+    def bs(self):
+        return (self.H + self.T) * self.C
+
+    def row(self, r):
+        """row r of item 0, counted from the first history row, as ops take an address: (tensor, element offset)"""
+        return (self.arena, self.off + r * self.C)
+
+    @property
+    def chunk(self):
+        """the first row of this call"""
+        return self.row(self.H)
+
+    def view(self):
+        return self.arena[self.off:self.off + self.B * self.bs].view(self.B, self.H + self.T, self.C)
+
+
+class HistoryArena:
+    """every [history | chunk] buffer of a causal plan, in ONE tensor -- so the carry of a stream (the last H rows of
+    each buffer move to its front) is a table of copies inside one tensor: srn_multi_copy, one launch per 160 (buffer,
+    item) pairs.  add() the buffers by name, allocate() once (zeros: the causal padding), then look them up."""
+
+    def __init__(self, B, dev):
+        self.B, self.dev, self._specs, self._bufs, self.t = B, dev, [], {}, None
+
+    def add(self, name, H, T, C):
+        assert self.t is None and name not in dict(self._specs)
+        self._specs.append((name, (H, T, C)))
+
+    def allocate(self):
+        off = 0
+        for name, (H, T, C) in self._specs:
+            self._bufs[name] = (off, H, T, C)
+            off += rup(self.B * (H + T) * C, 4)  # every buffer 16-byte aligned
+        self.t = torch.zeros(off, device=self.dev, dtype=torch.float32)
+        self._bufs = {n: HistBuf(self.t, o, self.B, H, T, C) for n, (o, H, T, C) in self._bufs.items()}
+
+    def __getitem__(self, name):
+        return self._bufs[name]
+
+    def carry_ops(self):
+        """the ops that end a chunk: rows [T, T + H) of every item of every buffer move to rows [0, H).  Where every
+        buffer has T >= H the two spans never overlap and the copies run in place; a chunk shorter than some history
+        goes through a scratch tensor of the spans (twice the launches), since a copy may not read what another
+        workgroup of the same launch writes."""
+        spans = []  # (source view, offset of its destination in the arena)
+        for hb in self._bufs.values():
+            if hb.H:
+                v = hb.view()
+                spans += [(v[b, hb.T:], hb.off + b * hb.bs) for b in range(self.B)]
+        if not spans:
+            return []
+        if all(hb.T >= hb.H for hb in self._bufs.values()):
+            return [ops.MultiCopyOp([v for v, _ in spans], [o for _, o in spans], self.t)]
+        at = [0]
+        for v, _ in spans:
+            at.append(at[-1] + v.numel())
+        scratch = torch.zeros(at[-1], device=self.dev, dtype=torch.float32)
+        return [ops.MultiCopyOp([v for v, _ in spans], at[:-1], scratch),
+                ops.MultiCopyOp([scratch[a:b] for a, b in zip(at[:-1], at[1:])], [o for _, o in spans], self.t)]
+
+
+def causal_unit_history(cv, C):
+    """rows of history in front of the input of causal unit `cv` of a C-channel stage: the fused unit recomputes its
+    intermediate from (k - 1)(d + 1) rows of x; the unfused one keeps the intermediate's k - 1 rows in a buffer of
+    their own and needs the first conv's (k - 1) d only"""
+    return (cv["k"] - 1) * (cv["d"] + 1) if fused_unit(cv, C) else (cv["k"] - 1) * cv["d"]
+
+
+def causal_stage_buffers(arena, i, blocks, C, T, H_next):
+    """the buffers of causal stage i: `u{i}` the up-sampled input, which every block reads (the longest history any of
+    them needs), `x{i}.{j}.{idx}` the input of unit idx >= 1 of block j, `t{i}.{j}.{idx}` the middle of an unfused
+    two-conv unit, `acc{i}` the stage's mean with the H_next rows its consumer reaches back"""
+    arena.add(f"u{i}", max(causal_unit_history(convs[0], C) for convs in blocks), T, C)
+    for j, convs in enumerate(blocks):
+        for idx, cv in enumerate(convs):
+            if idx:
+                arena.add(f"x{i}.{j}.{idx}", causal_unit_history(cv, C), T, C)
+            if "w2" in cv and not fused_unit(cv, C):
+                arena.add(f"t{i}.{j}.{idx}", cv["k"] - 1, T, C)
+    arena.add(f"acc{i}", H_next, T, C)
+
+
+def causal_upsample_ops(ol, B, src, up, out, slope, lead):
+    """CausalConvTranspose1d(k = 2 s, stride s), LeakyReLU in front (causal_conv.py:44-77): `src` a HistBuf with ONE
+    history row -- the previous chunk's last row, or, where lead[b] <= 0, a copy of this chunk's first
+    (ReplicationPad1d((1, 0)); LeakyReLU commutes with the copy) -- and per output phase one conv of two taps into the
+    chunk rows of `out`.  up: the packed entry (phases from ops.convtranspose_phases_causal, b, s, cout)."""
+    assert src.H == 1
+    s, co = up["s"], up["cout"]
+    ol.append(ops.replicate_first_row_op(src.row(0), src.bs, src.C, lead, B))
+    for r, (taps, wp) in enumerate(up["phases"]):
+        ol.append(conv_op(B, src.row(0), src.C, 1 + src.T, wp, up["b"], out.chunk, co, src.T, taps,
+                          pro_act=ops.ACT_LEAKY, pro_slope=slope, out_bs=out.bs, out_t_stride=s, out_t_off=r))
+
+
+def causal_mrf_stage_ops(ol, B, arena, i, blocks, C, T, slope, lead):
+    """mrf_stage_ops for causal stage i over the buffers of causal_stage_buffers: acc{i} = mean over `blocks` of
+    block(u{i}).  A unit reads a window of its input buffer that begins as many rows before the chunk as it reaches
+    back, and writes the chunk rows of the next unit's buffer: nothing a later chunk needs is overwritten (the dense
+    plan's ping-pong buffers would be).  lead: the stage's row of the plan's LeadTable, for the fused units."""
+    u, acc = arena[f"u{i}"], arena[f"acc{i}"]
+    nb = len(blocks)
+    for j, convs in enumerate(blocks):
+        x = u
+        for idx, cv in enumerate(convs):
+            last = idx == len(convs) - 1
+            dst = acc if last else arena[f"x{i}.{j}.{idx + 1}"]
+            k, d = cv["k"], cv["d"]
+            fin = {}
+            if last:
+                # cs += block(c); c = cs / num_blocks  (hifigan.py:183-186), in the reference's order
+                if j > 0:
+                    fin.update(res2=acc.chunk, res2_bs=acc.bs, ld_res2=C)
+                if j == nb - 1:
+                    fin.update(post=ops.POST_DIV, post_div=float(nb))
+            H = causal_unit_history(cv, C)
+            if fused_unit(cv, C):
+                ol.append(ops.ResUnitOp(x=x.row(x.H - H), x_bs=x.bs, w1=cv["w1"], b1=cv["b1"], w2=cv["w2"], b2=cv["b2"],
+                                        out=dst.chunk, out_bs=dst.bs, n_batch=B, T=T, C=C, k=k, dilation=d, slope=slope,
+                                        res2=fin.get("res2"), res2_bs=acc.bs, post_div=fin.get("post_div", 0.0),
+                                        lead=lead))
+            else:
+                skip = dict(res=x.chunk, res_mode=ops.RES_ADD, res_bs=x.bs, ld_res=C, out_bs=dst.bs, **fin)
+                first = dict(in_bs=x.bs, pro_act=ops.ACT_LEAKY, pro_slope=slope)
+                if "w2" in cv:
+                    xt = arena[f"t{i}.{j}.{idx}"]  # its k - 1 history rows: the intermediate of the chunk before
+                    ol.append(conv_op(B, x.row(x.H - H), C, H + T, cv["w1"], cv["b1"], xt.chunk, C, T,
+                                      range(0, k * d, d), out_bs=xt.bs, post=ops.POST_LEAKY, post_div=slope, **first))
+                    ol.append(conv_op(B, xt.row(0), C, k - 1 + T, cv["w2"], cv["b2"], dst.chunk, C, T, range(k), **skip))
+                else:
+                    ol.append(conv_op(B, x.row(x.H - H), C, H + T, cv["w1"], cv["b1"], dst.chunk, C, T,
+                                      range(0, k * d, d), **first, **skip))
+            x = dst
+
+
+class LeadTable:
+    """how far each item of a causal plan has come, at every rate: `scales` as LengthTable's, `lead` ONE (n_rates, B)
+    int32 device tensor -- row i holds, per item, the rows of its utterance that lie before the next call at rate i
+    (capped: the ops clamp it to their own history) -- `rows` its (B,) rows, which the ops read when they run.
+    set_pushed() rewrites the tensor in place, outside the captured graph, whose nodes only carry its address."""
+
+    CAP = 1 << 30
+
+    def __init__(self, upsample_scales, B, dev):
+        self.scales, self.B = [1], B
+        for s in upsample_scales:
+            self.scales.append(self.scales[-1] * s)
+        self.lead = torch.zeros(len(self.scales), B, dtype=torch.int32, device=dev)
+        self.rows = list(self.lead.unbind(0))
+
+    def set_pushed(self, frames):
+        """frames: the input frames every item has been given so far"""
+        host = torch.tensor([[min(int(frames) * s, self.CAP)] * self.B for s in self.scales], dtype=torch.int32)
+        self.lead.copy_(host)
 
 
 class LengthTable:

@@ -10,6 +10,10 @@ norm), so a parallel_wavegan-style checkpoint ``["model"]["generator"]`` loads u
 Everything is computed channels-last by libserenade_hip.so: the transposed convolutions run as one
 implicit-GEMM launch per output phase (2 taps each), every residual-stack conv has the LeakyReLU
 fused into its input gather and bias / residual / stage-mean fused into its epilogue.
+
+A generator with ``use_causal_conv`` (CausalConv1d / CausalConvTranspose1d, vocoder/layers/causal_conv.py) loads the
+reference's causal key names and, besides the calls above, vocodes in chunks: ``HiFiGANGenerator.stream`` /
+``Vocoder.stream`` (CausalHiFiGANPlan, HiFiGANStream).
 """
 import logging
 import os
@@ -21,10 +25,11 @@ import yaml
 from . import _shapes, ops
 from .models import _Packed, _fold_wn
 from .plan import FUSED_UNIT_CHANNELS  # noqa: F401  (its public name is vocoder.FUSED_UNIT_CHANNELS)
-from .plan import (LengthTable, conv_op, dev_f32, item_lengths, lru_get, masked, mrf_stage_ops,
+from .plan import (HistoryArena, LeadTable, LengthTable, causal_mrf_stage_ops, causal_stage_buffers,
+                   causal_upsample_ops, conv_op, dev_f32, item_lengths, lru_get, masked, mrf_stage_ops,
                    require_cuda as _require_cuda, rup, upsample_ops)
 
-__all__ = ["HiFiGANGenerator", "Vocoder", "load_vocoder", "hifigan_state_shapes"]
+__all__ = ["HiFiGANGenerator", "HiFiGANStream", "Vocoder", "VocoderStream", "load_vocoder", "hifigan_state_shapes"]
 
 
 def hifigan_state_shapes(**params):
@@ -81,14 +86,14 @@ class HiFiGANGenerator(_Generator):
         assert kernel_size % 2 == 1, "Kernel size must be odd number."
         assert len(upsample_scales) == len(upsample_kernel_sizes)
         assert len(resblock_dilations) == len(resblock_kernel_sizes)
-        assert not use_causal_conv, "causal HiFi-GAN is not reachable from the decode path (SURVEY section 2)"
         assert bias and out_channels == 1 and nonlinear_activation == "LeakyReLU"
         for s, k in zip(upsample_scales, upsample_kernel_sizes):
             assert k == 2 * s
         super().__init__(_shapes.hifigan_shapes(in_channels, out_channels, channels, kernel_size, upsample_scales,
                                                 upsample_kernel_sizes, resblock_kernel_sizes,
                                                 [tuple(d) for d in resblock_dilations], use_additional_convs,
-                                                weight_norm=use_weight_norm))
+                                                weight_norm=use_weight_norm, causal=use_causal_conv))
+        self.use_causal_conv = bool(use_causal_conv)
         self.in_channels, self.channels, self.kernel_size = in_channels, channels, kernel_size
         self.upsample_scales = tuple(upsample_scales)
         self.upsample_kernel_sizes = tuple(upsample_kernel_sizes)
@@ -123,36 +128,53 @@ class HiFiGANGenerator(_Generator):
         if self._packed is None:
             dev = self._device()
             sd = {k: dev_f32(v, dev) for k, v in self._own_state().items() if k not in ("mean", "scale")}
-            P = dict(in_w=ops.pack_conv_weight(_fold_wn(sd, "input_conv")), in_b=sd["input_conv.bias"], ups=[],
-                     blocks=[])
+            # the causal classes hold their conv one module deeper (causal_conv.py:27,62); the packed weights are the same
+            conv, deconv = (".conv", ".deconv") if self.use_causal_conv else ("", "")
+            P = dict(in_w=ops.pack_conv_weight(_fold_wn(sd, "input_conv" + conv)), in_b=sd[f"input_conv{conv}.bias"],
+                     ups=[], blocks=[])
             for i, s in enumerate(self.upsample_scales):
-                w = _fold_wn(sd, f"upsamples.{i}.1")
-                P["ups"].append(dict(phases=ops.convtranspose_phases(w, s, s // 2 + s % 2),
-                                     b=sd[f"upsamples.{i}.1.bias"], cin=w.shape[0], cout=w.shape[1], s=s))
+                w = _fold_wn(sd, f"upsamples.{i}.1" + deconv)
+                phases = (ops.convtranspose_phases_causal(w, s) if self.use_causal_conv
+                          else ops.convtranspose_phases(w, s, s // 2 + s % 2))
+                P["ups"].append(dict(phases=phases, b=sd[f"upsamples.{i}.1{deconv}.bias"], cin=w.shape[0],
+                                     cout=w.shape[1], s=s))
             for bi in range(self.num_upsamples * self.num_blocks):
                 j = bi % self.num_blocks
                 k, dil = self.resblock_kernel_sizes[j], self.resblock_dilations[j]
                 convs = []
                 for idx, d in enumerate(dil):
-                    p1 = f"blocks.{bi}.convs1.{idx}.1"
+                    p1 = f"blocks.{bi}.convs1.{idx}.1" + conv
                     c = dict(d=d, k=k, w1=ops.pack_conv_weight(_fold_wn(sd, p1)), b1=sd[p1 + ".bias"])
                     if self.use_additional_convs:
-                        p2 = f"blocks.{bi}.convs2.{idx}.1"
+                        p2 = f"blocks.{bi}.convs2.{idx}.1" + conv
                         c.update(w2=ops.pack_conv_weight(_fold_wn(sd, p2)), b2=sd[p2 + ".bias"])
                     convs.append(c)
                 P["blocks"].append(convs)
-            wo = _fold_wn(sd, "output_conv.1")  # (1, C, k)
+            wo = _fold_wn(sd, "output_conv.1" + conv)  # (1, C, k)
             P["out_w"] = wo[0].t().contiguous()  # (k, C)
-            P["out_b"] = sd["output_conv.1.bias"]
+            P["out_b"] = sd[f"output_conv.1{conv}.bias"]
             self._packed = P
         return self._packed
 
     def plan(self, B, T):
         key = (B, T, ops.DEFAULT_PRECISION)
-        return lru_get(self._plans, key, 4, lambda: HiFiGANPlan(self, B, T))
+        make = CausalHiFiGANPlan if self.use_causal_conv else HiFiGANPlan
+        return lru_get(self._plans, key, 4, lambda: make(self, B, T))
 
     def _ragged_slot(self):
-        return self._plans, ("ragged",), HiFiGANPlan  # the dense plans' LRU, the key tagged
+        # the dense plans' LRU, the key tagged.  A causal generator's ragged plan is its dense plan at the bucket's
+        # length plus one op that zeroes the tails (CausalHiFiGANPlan)
+        return self._plans, ("ragged",), CausalHiFiGANPlan if self.use_causal_conv else HiFiGANPlan
+
+    def stream(self, B, chunk_frames):
+        """a HiFiGANStream: B utterances vocoded side by side, at most chunk_frames frames per push().  Causal
+        generators only -- ValueError otherwise, and for chunk_frames < 1, before anything is built or launched."""
+        if not self.use_causal_conv:
+            raise ValueError("HiFiGANGenerator.stream: only a generator with use_causal_conv can be run in chunks "
+                             "(a non-causal output row depends on later input rows)")
+        if int(B) < 1 or int(chunk_frames) < 1:
+            raise ValueError(f"HiFiGANGenerator.stream: B = {B}, chunk_frames = {chunk_frames} must be at least 1")
+        return HiFiGANStream(self, int(B), int(chunk_frames))
 
     @torch.no_grad()
     def forward(self, c):
@@ -182,7 +204,10 @@ class HiFiGANGenerator(_Generator):
     def inference_batch(self, c, normalize_before=False, lengths=None):
         """(B, T, in_channels) -> (B, 1, T * hop)   (hifigan.py:267-284).  lengths (B frame counts in [1, T]): the
         batch is ragged -- item b is vocoded as its own B = 1 call on its first lengths[b] frames (the rows behind
-        them may hold anything) and the output is zero past lengths[b] * hop."""
+        them may hold anything) and the output is zero past lengths[b] * hop.
+        A causal generator runs its dense plan at the longest length and zeroes the output past lengths[b] * hop.  That
+        is exact: no output row of a causal generator depends on a later input row, so the first lengths[b] * hop
+        samples of item b are what its own B = 1 call gives, whatever the rows behind its end hold."""
         if not isinstance(c, torch.Tensor):
             c = torch.tensor(c, dtype=torch.float).to(self._device())
         _require_cuda(c, "HiFiGANGenerator.inference_batch")
@@ -264,6 +289,131 @@ class HiFiGANPlan:
 
     def run(self):
         self._runner()
+
+
+class CausalHiFiGANPlan:
+    """Buffers + op list of a causal generator (use_causal_conv) for B items of T frames: ONE builder for the one-shot
+    forward and for a stream's chunk.  Input: self.c_in (B, T, in_ch) channels-last; output: self.wave (B, T * hop).
+
+    Every conv reads a [history | chunk] buffer of its own (plan.HistoryArena) as a valid conv; histories of zeros are
+    the causal padding, self.lead (plan.LeadTable) tells the fused units and the replication pad of the up-sampling
+    how much of an item's utterance lies before this call.  The one-shot plan is this op list run with zero histories
+    and every lead 0: nothing it runs writes a history row, so it can be run again and again.  carry=True (a stream's
+    plan) appends the ops that move every buffer's last H rows to its front; HiFiGANStream advances the leads.
+
+    ragged=True: lengths as data the cheap way -- the dense causal plan at T frames, then self.wave zeroed past
+    lengths[b] * hop (set_lengths).  Exact, since no output row depends on a later input row."""
+
+    def __init__(self, gen, B, T, ragged=False, carry=False):
+        P = gen.packed()
+        dev = gen._device()
+        self.B, self.T = B, T
+        self.c_raw = None  # Vocoder's ragged batch in front of the renormalisation: allocated when first used
+        ks, cin, C0, n_up = gen.kernel_size, gen.in_channels, gen.channels, len(P["ups"])
+        nb = gen.num_blocks
+        arena = HistoryArena(B, dev)
+        arena.add("c", ks - 1, T, cin)
+        arena.add("h", 1, T, C0)
+        t = T
+        for i, up in enumerate(P["ups"]):
+            t *= up["s"]
+            causal_stage_buffers(arena, i, P["blocks"][i * nb:(i + 1) * nb], up["cout"], t, 1 if i + 1 < n_up else ks - 1)
+        arena.allocate()
+        self.arena = arena
+        self.leads = LeadTable(gen.upsample_scales, B, dev)
+        lead = self.leads.rows
+        self.c_in = torch.zeros(B, T, cin, device=dev, dtype=torch.float32)
+        self.wave = torch.zeros(B, t, device=dev, dtype=torch.float32)
+        c, h = arena["c"], arena["h"]
+        # c_in stays one contiguous (B, T, in_ch) tensor for its writers (srn_renorm, copy_); its rows go behind the
+        # input conv's history here
+        ol = [ops.copy_channels_op(self.c_in, T * cin, cin, 0, c.chunk, c.bs, cin, 0, B, T, cin),
+              conv_op(B, c.row(0), cin, ks - 1 + T, P["in_w"], P["in_b"], h.chunk, C0, T, range(ks), out_bs=h.bs)]
+        cur, tcur = h, T
+        for i, up in enumerate(P["ups"]):
+            causal_upsample_ops(ol, B, cur, up, arena[f"u{i}"], gen.slope, lead[i])
+            tcur *= up["s"]
+            causal_mrf_stage_ops(ol, B, arena, i, P["blocks"][i * nb:(i + 1) * nb], up["cout"], tcur, gen.slope,
+                                 lead[i + 1])
+            cur = arena[f"acc{i}"]
+        ol.append(ops.out_conv_tanh_causal_op(cur.row(0), P["out_w"], P["out_b"], self.wave, B, tcur, cur.C, ks, 0.01))
+        if ragged:
+            self.lens_out = torch.zeros(B, dtype=torch.int32, device=dev)
+            self._hop = tcur // T
+            ol.append(ops.zero_rows_ragged_op(self.wave, tcur, 1, self.lens_out, B, tcur))
+        if carry:
+            ol += arena.carry_ops()
+        self.ops = ol
+        self._runner = ops.GraphRunner(lambda: self.ops)
+
+    def set_lengths(self, lengths):
+        """lengths: B frame counts in [1, T] (validated by the caller, item_lengths); a ragged plan's only"""
+        self.lens_out.copy_(torch.tensor([int(n) * self._hop for n in lengths], dtype=torch.int32))
+
+    def restart(self):
+        """zero histories, every lead 0: the next run begins B new utterances"""
+        self.arena.t.zero_()
+        self.leads.set_pushed(0)
+
+    def run(self):
+        self._runner()
+
+
+class HiFiGANStream:
+    """B utterances through a causal generator, chunk by chunk: push() takes (B, n <= chunk_frames, in_channels) and
+    returns the next (B, n * hop) samples -- together, the chunks' outputs are the one-shot forward of the
+    concatenated input (no output row depends on a later input row; the few rows of state per conv live in the plan's
+    [history | chunk] buffers).  Every push runs the SAME op list (with graphs on, the same captured graph): what
+    differs between chunks is device data -- the carried histories and the leads.
+
+    A chunk shorter than chunk_frames is run padded (the rows behind it keep the previous chunk's) and the surplus
+    output dropped, which is exact for the same reason; it ends the stream, since the carried rows then are not the
+    utterance's last: push() after it raises until reset().  The stream runs on the generator's one plan for
+    (B, chunk_frames): two live streams of the same shape on one generator would share their state."""
+
+    def __init__(self, gen, B, chunk_frames):
+        self.gen, self.B, self.chunk_frames = gen, B, chunk_frames
+        self._pl = None
+        self.frames = 0  # pushed so far
+        self._ended = False
+
+    def _plan(self):
+        if self._pl is None:
+            g = self.gen
+            key = ("stream", self.B, self.chunk_frames, ops.DEFAULT_PRECISION)
+            self._pl = lru_get(g._plans, key, 4, lambda: CausalHiFiGANPlan(g, self.B, self.chunk_frames, carry=True))
+            self._pl.restart()
+        return self._pl
+
+    def check(self, c):
+        """ValueError unless `c` is a chunk this stream takes; nothing is built or launched"""
+        if c.dim() != 3 or c.shape[2] != self.gen.in_channels:
+            raise ValueError(f"HiFiGANStream.push: expected (B, n, {self.gen.in_channels}), got {tuple(c.shape)}")
+        if c.shape[0] != self.B:
+            raise ValueError(f"HiFiGANStream.push: the stream holds {self.B} utterances, the chunk {c.shape[0]}")
+        if not 1 <= c.shape[1] <= self.chunk_frames:
+            raise ValueError(f"HiFiGANStream.push: a chunk has 1 to {self.chunk_frames} frames, not {c.shape[1]}")
+        if self._ended:
+            raise ValueError("HiFiGANStream.push: a short chunk ended this stream; reset() begins the next")
+
+    @torch.no_grad()
+    def push(self, c):
+        self.check(c)
+        _require_cuda(c, "HiFiGANStream.push")
+        pl, n = self._plan(), c.shape[1]
+        pl.c_in[:, :n].copy_(c.detach())
+        pl.run()
+        y = pl.wave[:, :n * self.gen.hop].clone()
+        self.frames += n
+        self._ended = n < self.chunk_frames
+        pl.leads.set_pushed(self.frames)
+        return y
+
+    def reset(self):
+        """begin B new utterances"""
+        self.frames, self._ended = 0, False
+        if self._pl is not None:
+            self._pl.restart()
 
 
 def load_vocoder(checkpoint, config=None, stats=None):
@@ -372,6 +522,12 @@ class Vocoder(object):
         pl = self._decode_ragged(len(mels), max(lengths), lengths, fill)
         return [pl.wave[b, :n * self.model.hop].clone() for b, n in enumerate(lengths)]
 
+    def stream(self, B, chunk_frames):
+        """decode_batch in chunks, for a causal generator: a VocoderStream whose push() takes (B, n <= chunk_frames,
+        80) normalised mel and returns the next (B, n * hop) samples (HiFiGANGenerator.stream behind both
+        renormalisations)"""
+        return VocoderStream(self, self.model.stream(B, chunk_frames))
+
     def _decode_ragged(self, B, T_max, lengths, fill):
         """the padded batch goes through the one srn_renorm (all T_cap rows of every item: the rows past an item's end
         are renormalised leftovers, never read as data), then through the ragged plan"""
@@ -382,3 +538,25 @@ class Vocoder(object):
         fill(pl.c_raw)
         self._renorm_run(pl.c_raw, pl)
         return pl
+
+
+class VocoderStream:
+    """Vocoder.stream: a HiFiGANStream behind the two affine maps of Vocoder.decode (vocoder.py:52-56)"""
+
+    def __init__(self, vocoder, stream):
+        self.vocoder, self.stream = vocoder, stream
+
+    @torch.no_grad()
+    def push(self, c):
+        self.stream.check(c)
+        _require_cuda(c, "VocoderStream.push")
+        v = self.vocoder
+        c = c.detach().to(torch.float32).contiguous()
+        y = torch.empty_like(c)
+        ts = v.trg_stats if v.take_norm_feat else {"scale": None, "mean": None}
+        ops.renorm_op(c, ts["scale"], ts["mean"], v.stats["mean"], v.stats["scale"], y, c.shape[0] * c.shape[1],
+                      c.shape[2])()
+        return self.stream.push(y)
+
+    def reset(self):
+        self.stream.reset()

@@ -11,6 +11,10 @@ decode CLI drives it.  Prints one JSON object.
                                     graphs on -- capture included), (b) one `decode_ragged` call per batch, at bucket
                                     sizes 1, 32, 64 and 128 frames (plans reused where a batch falls into a bucket seen
                                     before, dead frames up to the bucket's end computed)
+    --causal                        the generator with use_causal_conv=True: the same calls
+    --stream N                      (implies --causal; may be given several times) besides the one-shot call, the same
+                                    B x T frames through `Vocoder.stream(B, N)` in chunks of N frames: wall time for the
+                                    whole batch, per chunk, and from reset() to the first chunk's samples on the host
     --graphs                        replay plans as captured hipGraphs (ops.set_graphs)
     --passes N                      batches of fresh lengths per measurement (default 6)
 
@@ -32,10 +36,10 @@ from serenade_amd.utils.synth import HIFIGAN_PARAMS, fill_state_dict  # noqa: E4
 BUCKETS = (1, 32, 64, 128)
 
 
-def make_vocoder(dev):
-    gen = vocoder.HiFiGANGenerator(**HIFIGAN_PARAMS)
-    gen.load_state_dict(fill_state_dict(_shapes.as_meta(_shapes.hifigan_shapes(**HIFIGAN_PARAMS, weight_norm=True)),
-                                        seed=0))
+def make_vocoder(dev, causal=False):
+    params = dict(HIFIGAN_PARAMS, use_causal_conv=causal)
+    gen = vocoder.HiFiGANGenerator(**params)
+    gen.load_state_dict(fill_state_dict(_shapes.as_meta(_shapes.hifigan_shapes(**params, weight_norm=True)), seed=0))
     one = np.ones(80, dtype=np.float32)
     return vocoder.Vocoder.from_generator(gen, {"sampling_rate": 24000}, {"mean": 0 * one, "scale": one}, dev,
                                           trg_stats={"mean": 0 * one, "scale": one})
@@ -82,21 +86,30 @@ def by_len_loop(voc, mels):
 
 
 def main():
-    args = [v for v in sys.argv[1:] if not v.startswith("--")]
-    flags = [v for v in sys.argv[1:] if v.startswith("--")]
-    passes = 6
-    if "--passes" in flags:
-        passes = int(args.pop(2))
-    if set(flags) - {"--ragged", "--graphs", "--passes"}:
+    args, flags, passes, chunks = [], [], 6, []
+    argv = sys.argv[1:]
+    while argv:
+        v = argv.pop(0)
+        if v in ("--passes", "--stream"):
+            if not argv:
+                sys.exit(__doc__)
+            n = int(argv.pop(0))
+            if v == "--passes":
+                passes = n
+            else:
+                chunks.append(n)
+        (flags if v.startswith("--") else args).append(v)
+    if set(flags) - {"--ragged", "--graphs", "--passes", "--causal", "--stream"}:
         sys.exit(__doc__)
     B, T = (int(v) for v in (args[:2] + ["8", "1024"][len(args):]))
     dev = torch.device("cuda:0")
     ops.set_graphs("--graphs" in flags)
-    voc = make_vocoder(dev)
+    causal = "--causal" in flags or bool(chunks)
+    voc = make_vocoder(dev, causal)
     hop = voc.model.hop
     rng = np.random.default_rng(0)
     pool = torch.from_numpy(rng.standard_normal((B, T, 80)).astype(np.float32)).to(dev)
-    out = {"build_id": build.built_id(), "graphs": "--graphs" in flags, "passes": passes,
+    out = {"build_id": build.built_id(), "graphs": "--graphs" in flags, "passes": passes, "causal": causal,
            "workload": f"B={B} utterances x {T} frames, hop {hop}"}
 
     def rate(dt, frames):
@@ -104,6 +117,21 @@ def main():
 
     with torch.no_grad():
         out["dense_equal"] = rate(_timed(lambda: voc.decode_batch(pool), 3, 10), B * T)
+        for n in chunks:
+            st = voc.stream(B, n)
+            pieces = [pool[:, t:t + n] for t in range(0, T, n)]
+
+            def whole():
+                st.reset()
+                for c in pieces:
+                    st.push(c)
+
+            def first():
+                st.reset()
+                return st.push(pieces[0]).cpu()
+            dt = _timed(whole, 2, 5)
+            out[f"stream_{n}"] = dict(rate(dt, B * T), chunks=len(pieces), ms_per_chunk=dt * 1e3 / len(pieces),
+                                      first_chunk_ms=_timed(first, 2, 10) * 1e3)
         if "--ragged" in flags:
             full = [T] * B
             out["ragged_equal"] = rate(_timed(lambda: voc.decode_batch(pool, lengths=full), 3, 10), B * T)
