@@ -374,6 +374,31 @@ int srn_zero_rows_ragged(float* x, int64_t bs, int n_cols, const int32_t* n_rows
  * of n_cols contiguous floats back to back; where lead[b] > 0 the item is not touched (row 0 holds the last row of the
  * chunk before).  lead: device, B int32.  NULL pointers, non-positive sizes and overlapping items are refused. */
 int srn_replicate_first_row(float* x, int64_t bs, int n_cols, const int32_t* lead, int B, void* stream);
+/* The state a chunked causal generator keeps between calls (the few input rows each CausalConv1d reaches back,
+ * vocoder/layers/causal_conv.py:11-41, which the reference recomputes from the whole utterance), moved on with the
+ * pushed frame counts as device data: ONE launch for every [history | chunk] buffer of a plan and every item.  Entry e
+ * describes a buffer inside `arena`: item b at arena + off + b * bs holds H + T rows of C contiguous floats, `scale`
+ * rows per input frame.  n: device, B int32.  For item b of entry e, with m = min(n[b], T / scale) * scale:
+ *   n[b] < 0   rows [0, H) become +0.0 (a new utterance begins: zero history is the causal padding);
+ *   n[b] == 0  nothing is written (the item was idle, its state stays);
+ *   n[b] > 0   rows [0, H) take the values rows [m, m + H) held before the launch -- the snapshot (memmove) result where
+ *              the two spans overlap (m < H), with no scratch pass: one workgroup owns a (buffer, item) pair and reads
+ *              a block into registers before it stores it.
+ * Rows at or past H are never written, rows at or past m + H never read.  The table is passed by value in the kernel
+ * arguments.  NULL pointers, B outside [1, 65535], n outside [1, SRN_CARRY_MAX], an entry with off < 0, H < 0, T < 0,
+ * C < 1 or scale < 1, and items that overlap (bs < (H + T) C with B > 1) are refused before any launch. */
+#define SRN_CARRY_MAX 96
+typedef struct SrnCarryEntry {
+  int64_t off;
+  int64_t bs;
+  int32_t H, T, C, scale;
+} SrnCarryEntry;
+typedef struct SrnCarryTable {
+  int32_t n;
+  int32_t pad_;
+  SrnCarryEntry e[SRN_CARRY_MAX];
+} SrnCarryTable;
+int srn_history_carry_ragged(float* arena, const SrnCarryTable* table, const int32_t* n, int B, void* stream);
 
 /* StyleTokenLayer (style_encoder.py:235-252 + gst/attention.py:110-184,298-300): ref (B, Dq) -> out (B, F), with its
  * input-independent parts formed at weight-packing time: k, v (n_tok, F) = tanh(embs) W_k^T + b_k / W_v^T + b_v;

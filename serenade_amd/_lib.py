@@ -65,6 +65,17 @@ class SrnCopyList(ctypes.Structure):
                 ("off", c_int64 * SRN_COPY_LIST_MAX), ("len", c_int64 * SRN_COPY_LIST_MAX)]
 
 
+SRN_CARRY_MAX = 96
+
+
+class SrnCarryEntry(ctypes.Structure):
+    _fields_ = [("off", c_int64), ("bs", c_int64), ("H", c_int32), ("T", c_int32), ("C", c_int32), ("scale", c_int32)]
+
+
+class SrnCarryTable(ctypes.Structure):
+    _fields_ = [("n", c_int32), ("pad_", c_int32), ("e", SrnCarryEntry * SRN_CARRY_MAX)]
+
+
 class SrnWorldParams(ctypes.Structure):
     _fields_ = [
         ("n_batch", c_int32), ("max_frames", c_int32), ("fs", c_int32), ("fft_size", c_int32),
@@ -154,6 +165,7 @@ _SIGS = {
     "srn_gru_recur_last_ragged": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "srn_zero_rows_ragged": (c_int, [_P, c_int64, c_int, _P, c_int, c_int, _P]),
     "srn_replicate_first_row": (c_int, [_P, c_int64, c_int, _P, c_int, _P]),
+    "srn_history_carry_ragged": (c_int, [_P, POINTER(SrnCarryTable), _P, c_int, _P]),
     "srn_style_token_attention_kv": (c_int, [_P] * 8 + [c_int] * 5 + [_P]),
     "srn_rowln_fwd": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int, c_float, _P]),
     "srn_rowln_bwd": (c_int, [_P, _P, _P, c_int64, _P, _P, c_int, c_int, c_int, c_float, _P]),

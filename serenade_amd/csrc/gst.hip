@@ -68,6 +68,52 @@ __global__ __launch_bounds__(256) void replicate_first_row_kernel(float* __restr
   if (c < n_cols) xb[c] = xb[n_cols + c];
 }
 
+// The carry of a causal stream with the pushed counts as device data (srn_history_carry_ragged).  Grid (entries, B):
+// ONE workgroup owns a (buffer, item) pair, so nothing it reads is written by another workgroup, and the table travels
+// in the kernel arguments (the call can sit inside a captured hipGraph).  n[b] is one scalar load, uniform over the
+// workgroup; an idle item (n[b] == 0) costs that load only.  With m = min(n[b], T / scale) * scale rows pushed, floats
+// [m C, (m + H) C) of the item move to [0, H C): the destination lies below the source, so the copy runs upwards in
+// blocks of HC_BLOCK floats, each block read into registers by all threads BEFORE any of them stores it (one barrier
+// per block).  That is the snapshot (memmove) result for every m >= 1 without a scratch pass: block j's stores end
+// where its loads begin or before, later blocks read only above them, and no thread stores block j + 1 before every
+// thread has passed the barrier behind block j's loads.
+constexpr int HC_THREADS = 256;
+constexpr int HC_PER_THREAD = 8;
+constexpr int HC_BLOCK = HC_THREADS * HC_PER_THREAD;
+
+__global__ __launch_bounds__(HC_THREADS) void history_carry_ragged_kernel(float* __restrict__ arena,
+                                                                          const SrnCarryTable table, SrnLens n) {
+  const SrnCarryEntry e = table.e[blockIdx.x];
+  const int b = blockIdx.y;
+  const int nb = n[b];  // one scalar load, uniform over the workgroup
+  const int64_t total = (int64_t)e.H * e.C;
+  if (nb == 0 || total == 0) return;  // uniform: the item was idle, its state stays
+  float* x = arena + e.off + (int64_t)b * e.bs;
+  if (nb < 0) {  // a restart: zero history is the causal padding
+    for (int64_t i = threadIdx.x; i < total; i += HC_THREADS) x[i] = 0.f;
+    return;
+  }
+  const int64_t shift = (int64_t)min(nb, e.T / e.scale) * e.scale * e.C;  // m C, with m <= T
+  if (shift == 0) return;  // uniform: T < scale, no whole frame fits
+  for (int64_t i0 = 0; i0 < total; i0 += HC_BLOCK) {  // the bounds are uniform: every thread meets every barrier
+    float v[HC_PER_THREAD];
+#pragma unroll
+    for (int u = 0; u < HC_PER_THREAD; ++u) {
+      const int64_t i = i0 + u * HC_THREADS + threadIdx.x;
+      v[u] = i < total ? x[shift + i] : 0.f;
+    }
+    // the loads have RETURNED before any wave stores: __syncthreads alone leaves them in flight across the barrier
+    // (its workgroup-scope fence counts on the CU's in-order memory path), and this kernel should not lean on that
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0); expcnt and lgkmcnt not waited for (gfx9 encoding)
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < HC_PER_THREAD; ++u) {
+      const int64_t i = i0 + u * HC_THREADS + threadIdx.x;
+      if (i < total) x[i] = v[u];
+    }
+  }
+}
+
 // Style-token attention on PRECOMPUTED keys / values: K = tanh(embs) W_k^T + b_k and V likewise do not depend on the
 // input, so they are formed once at weight-packing time ((n_tok, F) each); the query / output projections read
 // TRANSPOSED weights (wq_t [Dq][F], wo_t [F][F]) so lanes read consecutive addresses.  One workgroup per batch item.
@@ -150,6 +196,27 @@ extern "C" int srn_replicate_first_row(float* x, int64_t bs, int n_cols, const i
                 (long long)bs);
   hipLaunchKernelGGL(replicate_first_row_kernel, dim3((unsigned)((n_cols + 255) / 256), B), dim3(256), 0,
                      (hipStream_t)stream, x, bs, n_cols, lead);
+  SRN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int srn_history_carry_ragged(float* arena, const SrnCarryTable* table, const int32_t* n, int B,
+                                        void* stream) {
+  SRN_CHECK_ARG(arena && table && n, "history_carry_ragged: null");
+  SRN_CHECK_ARG(B > 0 && B <= 65535, "history_carry_ragged: bad batch %d", B);
+  SRN_CHECK_ARG(table->n > 0 && table->n <= SRN_CARRY_MAX, "history_carry_ragged: %d entries, 1 to %d are taken",
+                table->n, SRN_CARRY_MAX);
+  for (int i = 0; i < table->n; ++i) {
+    const SrnCarryEntry& e = table->e[i];
+    SRN_CHECK_ARG(e.off >= 0 && e.H >= 0 && e.T >= 0 && e.C >= 1 && e.scale >= 1,
+                  "history_carry_ragged: entry %d: off %lld, H %d, T %d, C %d, scale %d", i, (long long)e.off, e.H, e.T,
+                  e.C, e.scale);
+    SRN_CHECK_ARG(B == 1 || e.bs >= ((int64_t)e.H + e.T) * e.C,
+                  "history_carry_ragged: entry %d: items of %lld floats overlap at a batch stride of %lld", i,
+                  (long long)(((int64_t)e.H + e.T) * e.C), (long long)e.bs);
+  }
+  hipLaunchKernelGGL(history_carry_ragged_kernel, dim3((unsigned)table->n, B), dim3(HC_THREADS), 0,
+                     (hipStream_t)stream, arena, *table, n);
   SRN_CHECK_LAUNCH();
   return 0;
 }

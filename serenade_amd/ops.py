@@ -517,6 +517,26 @@ def replicate_first_row_op(x, bs, n_cols, lead, B):
     return CallOp("srn_replicate_first_row", (x, bs, n_cols, lead, B))
 
 
+def history_carry_ragged_ops(arena, entries, n, B):
+    """n (_item_lens): for every entry (off, bs, H, T, C, scale) -- a [history | chunk] buffer inside `arena`, item b at
+    float off + b * bs, H + T rows of C floats, `scale` rows per input frame -- and every item b, rows [0, H) become
+    zero where n[b] < 0, stay where n[b] == 0, and take rows [m, m + H) with m = min(n[b], T // scale) * scale where
+    n[b] > 0 (overlapping spans as a snapshot).  One launch per _lib.SRN_CARRY_MAX entries; the table travels in the
+    kernel arguments, so the calls can sit inside a captured hipGraph."""
+    n = _item_lens(n, B, "history_carry_ragged_ops")
+    entries = [tuple(int(v) for v in e) for e in entries]
+    out = []
+    for i0 in range(0, len(entries), _lib.SRN_CARRY_MAX):
+        table = _lib.SrnCarryTable()
+        chunk = entries[i0:i0 + _lib.SRN_CARRY_MAX]
+        table.n = len(chunk)
+        for j, (off, bs, H, T, C, scale) in enumerate(chunk):
+            e = table.e[j]
+            e.off, e.bs, e.H, e.T, e.C, e.scale = off, bs, H, T, C, scale
+        out.append(CallOp("srn_history_carry_ragged", (arena, table, n, B)))
+    return out
+
+
 def style_token_attention_kv_op(ref, wq_t, bq, k, v, wo_t, bo, out, B, Dq, n_tok, F, n_head):
     return CallOp("srn_style_token_attention_kv", (ref, wq_t, bq, k, v, wo_t, bo, out, B, Dq, n_tok, F, n_head))
 

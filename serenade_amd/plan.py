@@ -225,6 +225,15 @@ class HistoryArena:
         return [ops.MultiCopyOp([v for v, _ in spans], at[:-1], scratch),
                 ops.MultiCopyOp([scratch[a:b] for a, b in zip(at[:-1], at[1:])], [o for _, o in spans], self.t)]
 
+    def carry_ragged_ops(self, n, frames):
+        """carry_ops with the pushed counts as device data (srn_history_carry_ragged): for item b of every buffer, rows
+        [0, H) are zeroed where n[b] < 0, kept where n[b] == 0, and take rows [n[b] scale, n[b] scale + H) where n[b] > 0
+        -- scale = T / frames the buffer's rows per input frame, `frames` the plan's chunk length.  n: (B,) int32 device
+        tensor, read when the ops run.  One launch per 96 buffers, no scratch: the kernel owns the overlap."""
+        assert all(hb.T % frames == 0 for hb in self._bufs.values())
+        table = [(hb.off, hb.bs, hb.H, hb.T, hb.C, hb.T // frames) for hb in self._bufs.values() if hb.H]
+        return ops.history_carry_ragged_ops(self.t, table, n, self.B) if table else []
+
 
 def causal_unit_history(cv, C):
     """rows of history in front of the input of causal unit `cv` of a C-channel stage: the fused unit recomputes its
@@ -318,6 +327,13 @@ class LeadTable:
     def set_pushed(self, frames):
         """frames: the input frames every item has been given so far"""
         host = torch.tensor([[min(int(frames) * s, self.CAP)] * self.B for s in self.scales], dtype=torch.int32)
+        self.lead.copy_(host)
+
+    def set_pushed_items(self, frames):
+        """frames: per item, the input frames it has been given since its utterance began (B values)"""
+        frames = [int(f) for f in frames]
+        assert len(frames) == self.B
+        host = torch.tensor([[min(f * s, self.CAP) for f in frames] for s in self.scales], dtype=torch.int32)
         self.lead.copy_(host)
 
 

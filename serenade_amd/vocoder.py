@@ -13,7 +13,8 @@ fused into its input gather and bias / residual / stage-mean fused into its epil
 
 A generator with ``use_causal_conv`` (CausalConv1d / CausalConvTranspose1d, vocoder/layers/causal_conv.py) loads the
 reference's causal key names and, besides the calls above, vocodes in chunks: ``HiFiGANGenerator.stream`` /
-``Vocoder.stream`` (CausalHiFiGANPlan, HiFiGANStream).
+``Vocoder.stream`` (CausalHiFiGANPlan, HiFiGANStream); with ``ragged=True`` as B independent sessions that start, idle
+and end one by one (HiFiGANSessionStream, VocoderSessions).
 """
 import logging
 import os
@@ -29,7 +30,8 @@ from .plan import (HistoryArena, LeadTable, LengthTable, causal_mrf_stage_ops, c
                    causal_upsample_ops, conv_op, dev_f32, item_lengths, lru_get, masked, mrf_stage_ops,
                    require_cuda as _require_cuda, rup, upsample_ops)
 
-__all__ = ["HiFiGANGenerator", "HiFiGANStream", "Vocoder", "VocoderStream", "load_vocoder", "hifigan_state_shapes"]
+__all__ = ["HiFiGANGenerator", "HiFiGANStream", "HiFiGANSessionStream", "Vocoder", "VocoderStream",
+           "VocoderSessionStream", "VocoderSessions", "load_vocoder", "hifigan_state_shapes"]
 
 
 def hifigan_state_shapes(**params):
@@ -166,15 +168,16 @@ class HiFiGANGenerator(_Generator):
         # length plus one op that zeroes the tails (CausalHiFiGANPlan)
         return self._plans, ("ragged",), CausalHiFiGANPlan if self.use_causal_conv else HiFiGANPlan
 
-    def stream(self, B, chunk_frames):
+    def stream(self, B, chunk_frames, ragged=False):
         """a HiFiGANStream: B utterances vocoded side by side, at most chunk_frames frames per push().  Causal
-        generators only -- ValueError otherwise, and for chunk_frames < 1, before anything is built or launched."""
+        generators only -- ValueError otherwise, and for chunk_frames < 1, before anything is built or launched.
+        ragged=True: a HiFiGANSessionStream -- B independent sessions, push(c, lengths, restart)."""
         if not self.use_causal_conv:
             raise ValueError("HiFiGANGenerator.stream: only a generator with use_causal_conv can be run in chunks "
                              "(a non-causal output row depends on later input rows)")
         if int(B) < 1 or int(chunk_frames) < 1:
             raise ValueError(f"HiFiGANGenerator.stream: B = {B}, chunk_frames = {chunk_frames} must be at least 1")
-        return HiFiGANStream(self, int(B), int(chunk_frames))
+        return (HiFiGANSessionStream if ragged else HiFiGANStream)(self, int(B), int(chunk_frames))
 
     @torch.no_grad()
     def forward(self, c):
@@ -301,6 +304,12 @@ class CausalHiFiGANPlan:
     and every lead 0: nothing it runs writes a history row, so it can be run again and again.  carry=True (a stream's
     plan) appends the ops that move every buffer's last H rows to its front; HiFiGANStream advances the leads.
 
+    carry="ragged" (HiFiGANSessionStream's plan): B independent sessions.  In front, one srn_history_carry_ragged over
+    the restart flags zeroes the histories of the items that begin an utterance; behind the compute ops, self.wave is
+    zeroed past lengths[b] * hop; last, one srn_history_carry_ragged over the pushed counts moves each item's rows
+    [n_b scale, n_b scale + H) to the front (an idle item keeps its state).  set_push() rewrites the counts, the flags
+    and the per-item leads in place.
+
     ragged=True: lengths as data the cheap way -- the dense causal plan at T frames, then self.wave zeroed past
     lengths[b] * hop (set_lengths).  Exact, since no output row depends on a later input row."""
 
@@ -341,7 +350,18 @@ class CausalHiFiGANPlan:
             self.lens_out = torch.zeros(B, dtype=torch.int32, device=dev)
             self._hop = tcur // T
             ol.append(ops.zero_rows_ragged_op(self.wave, tcur, 1, self.lens_out, B, tcur))
-        if carry:
+        if carry == "ragged":
+            # a stream of B independent sessions: what differs between pushes is self.push (restart, frames pushed and
+            # samples valid per item) and the leads, all rewritten in place by set_push() outside the captured graph
+            if ragged:
+                raise ValueError("CausalHiFiGANPlan: carry='ragged' zeroes the tails itself; ragged=True is the "
+                                 "one-shot form")
+            self.push = torch.zeros(3, B, dtype=torch.int32, device=dev)
+            restart, pushed, valid = self.push.unbind(0)
+            self._hop = tcur // T
+            ol = (arena.carry_ragged_ops(restart, T) + ol + [ops.zero_rows_ragged_op(self.wave, tcur, 1, valid, B, tcur)]
+                  + arena.carry_ragged_ops(pushed, T))
+        elif carry:
             ol += arena.carry_ops()
         self.ops = ol
         self._runner = ops.GraphRunner(lambda: self.ops)
@@ -349,6 +369,15 @@ class CausalHiFiGANPlan:
     def set_lengths(self, lengths):
         """lengths: B frame counts in [1, T] (validated by the caller, item_lengths); a ragged plan's only"""
         self.lens_out.copy_(torch.tensor([int(n) * self._hop for n in lengths], dtype=torch.int32))
+
+    def set_push(self, lengths, restart, before):
+        """a carry="ragged" plan's only, before each run: item b gives lengths[b] frames in [0, T], begins a new
+        utterance with them where restart[b], and had `before[b]` frames of this utterance before this run (0 where it
+        restarts); all validated by the caller"""
+        host = torch.tensor([[-1 if r else 0 for r in restart], [int(n) for n in lengths],
+                             [int(n) * self._hop for n in lengths]], dtype=torch.int32)
+        self.push.copy_(host)
+        self.leads.set_pushed_items(before)
 
     def restart(self):
         """zero histories, every lead 0: the next run begins B new utterances"""
@@ -414,6 +443,67 @@ class HiFiGANStream:
         self.frames, self._ended = 0, False
         if self._pl is not None:
             self._pl.restart()
+
+
+def _per_item(values, B, what, name):
+    """B per-item values (tensor, numpy or sequence) as a list; ValueError unless there are B"""
+    vals = list(values.tolist() if hasattr(values, "tolist") else values)
+    if len(vals) != B:
+        raise ValueError(f"{what}: {name} holds {len(vals)} values, the stream {B} sessions")
+    return vals
+
+
+class HiFiGANSessionStream:
+    """B independent sessions through a causal generator (HiFiGANGenerator.stream(..., ragged=True)): push(c, lengths,
+    restart) takes c (B, n_max <= chunk_frames, in_channels), of which item b gives its first lengths[b] in [0, n_max]
+    frames, and returns (B, n_max * hop), zero past lengths[b] * hop.  Item b begins a new utterance with this chunk
+    where restart[b]; every slot begins restarted.
+
+    Between two restarts, the concatenation of item b's valid output is the generator's one-shot call on the
+    concatenation of its valid input.  Rows of c at or past lengths[b] are never read as data (they may hold NaN), and
+    neither is another item's state; an item that gives no frames keeps its state, so a short or empty chunk ends
+    nothing.  Every push runs the SAME op list (with graphs on, the same captured graph): the lengths, the restart
+    flags and the leads are device data (CausalHiFiGANPlan carry="ragged").  The stream owns its plan -- it is not taken
+    from the generator's plan cache -- so two live streams never share state."""
+
+    def __init__(self, gen, B, chunk_frames):
+        self.gen, self.B, self.chunk_frames = gen, B, chunk_frames
+        self._pl = None
+        self.frames = [0] * B  # per session, pushed since its utterance began
+
+    def _plan(self):
+        if self._pl is None:
+            self._pl = CausalHiFiGANPlan(self.gen, self.B, self.chunk_frames, carry="ragged")
+        return self._pl
+
+    def check(self, c, lengths, restart=None):
+        """ValueError unless (c, lengths, restart) is a push this stream takes; nothing is built or launched.  Returns
+        the lengths as ints and the restart flags as bools."""
+        what = "HiFiGANSessionStream.push"
+        if c.dim() != 3 or c.shape[2] != self.gen.in_channels:
+            raise ValueError(f"{what}: expected (B, n, {self.gen.in_channels}), got {tuple(c.shape)}")
+        if c.shape[0] != self.B:
+            raise ValueError(f"{what}: the stream holds {self.B} sessions, the chunk {c.shape[0]}")
+        if not 1 <= c.shape[1] <= self.chunk_frames:
+            raise ValueError(f"{what}: a chunk has 1 to {self.chunk_frames} frames, not {c.shape[1]}")
+        lens = [int(n) for n in _per_item(lengths, self.B, what, "lengths")]
+        if min(lens) < 0 or max(lens) > c.shape[1]:
+            raise ValueError(f"{what}: lengths {tuple(lens)} must lie in [0, {c.shape[1]}]")
+        flags = [False] * self.B if restart is None else [bool(r) for r in _per_item(restart, self.B, what, "restart")]
+        return lens, flags
+
+    @torch.no_grad()
+    def push(self, c, lengths, restart=None):
+        lens, flags = self.check(c, lengths, restart)
+        _require_cuda(c, "HiFiGANSessionStream.push")
+        pl, n_max = self._plan(), c.shape[1]
+        before = [0 if r else f for r, f in zip(flags, self.frames)]
+        pl.set_push(lens, flags, before)
+        pl.c_in[:, :n_max].copy_(c.detach())
+        pl.run()
+        y = pl.wave[:, :n_max * self.gen.hop].clone()
+        self.frames = [f + n for f, n in zip(before, lens)]
+        return y
 
 
 def load_vocoder(checkpoint, config=None, stats=None):
@@ -522,10 +612,12 @@ class Vocoder(object):
         pl = self._decode_ragged(len(mels), max(lengths), lengths, fill)
         return [pl.wave[b, :n * self.model.hop].clone() for b, n in enumerate(lengths)]
 
-    def stream(self, B, chunk_frames):
+    def stream(self, B, chunk_frames, ragged=False):
         """decode_batch in chunks, for a causal generator: a VocoderStream whose push() takes (B, n <= chunk_frames,
         80) normalised mel and returns the next (B, n * hop) samples (HiFiGANGenerator.stream behind both
-        renormalisations)"""
+        renormalisations).  ragged=True: a VocoderSessionStream -- B independent sessions, push(c, lengths, restart)."""
+        if ragged:
+            return VocoderSessionStream(self, self.model.stream(B, chunk_frames, ragged=True))
         return VocoderStream(self, self.model.stream(B, chunk_frames))
 
     def _decode_ragged(self, B, T_max, lengths, fill):
@@ -540,6 +632,16 @@ class Vocoder(object):
         return pl
 
 
+def _renormed(v, c):
+    """a chunk (B, n, 80) through the two affine maps of Vocoder `v` (vocoder.py:52-56) in ONE srn_renorm, into a
+    tensor of its own"""
+    c = c.detach().to(torch.float32).contiguous()
+    y = torch.empty_like(c)
+    ts = v.trg_stats if v.take_norm_feat else {"scale": None, "mean": None}
+    ops.renorm_op(c, ts["scale"], ts["mean"], v.stats["mean"], v.stats["scale"], y, c.shape[0] * c.shape[1], c.shape[2])()
+    return y
+
+
 class VocoderStream:
     """Vocoder.stream: a HiFiGANStream behind the two affine maps of Vocoder.decode (vocoder.py:52-56)"""
 
@@ -550,13 +652,102 @@ class VocoderStream:
     def push(self, c):
         self.stream.check(c)
         _require_cuda(c, "VocoderStream.push")
-        v = self.vocoder
-        c = c.detach().to(torch.float32).contiguous()
-        y = torch.empty_like(c)
-        ts = v.trg_stats if v.take_norm_feat else {"scale": None, "mean": None}
-        ops.renorm_op(c, ts["scale"], ts["mean"], v.stats["mean"], v.stats["scale"], y, c.shape[0] * c.shape[1],
-                      c.shape[2])()
-        return self.stream.push(y)
+        return self.stream.push(_renormed(self.vocoder, c))
 
     def reset(self):
         self.stream.reset()
+
+
+class VocoderSessionStream:
+    """Vocoder.stream(..., ragged=True): a HiFiGANSessionStream behind the two affine maps of Vocoder.decode
+    (vocoder.py:52-56).  Rows of c past an item's length are renormalised like the rest and never read as data."""
+
+    def __init__(self, vocoder, stream):
+        self.vocoder, self.stream = vocoder, stream
+
+    @torch.no_grad()
+    def push(self, c, lengths, restart=None):
+        lens, flags = self.stream.check(c, lengths, restart)
+        _require_cuda(c, "VocoderSessionStream.push")
+        return self.stream.push(_renormed(self.vocoder, c), lens, flags)
+
+
+class VocoderSessions:
+    """Live sessions over ONE VocoderSessionStream of `slots` items, host bookkeeping only (no threads): open() gives a
+    free slot, feed(slot, mel) queues (n, 80) normalised mel frames, step() takes up to chunk_frames queued frames from
+    every open slot, runs one push and returns {slot: the next waveform samples} for the slots that gave frames,
+    close(slot) frees the slot once its queue is drained.  A reopened slot begins a new utterance."""
+
+    def __init__(self, vocoder, slots, chunk_frames):
+        self.stream = vocoder.stream(slots, chunk_frames, ragged=True)
+        self.vocoder, self.slots, self.chunk_frames = vocoder, int(slots), int(chunk_frames)
+        self._queue = [None] * self.slots    # per slot: its queued (n, 80) pieces; None: the slot is free
+        self._fresh = [False] * self.slots   # opened, not pushed yet: its next push restarts it
+        self._closing = [False] * self.slots
+
+    def open(self):
+        for slot, q in enumerate(self._queue):
+            if q is None:
+                self._queue[slot], self._fresh[slot], self._closing[slot] = [], True, False
+                return slot
+        raise RuntimeError(f"VocoderSessions.open: all {self.slots} slots are in use")
+
+    def _live(self, slot, what):
+        if not (isinstance(slot, int) and 0 <= slot < self.slots) or self._queue[slot] is None:
+            raise ValueError(f"VocoderSessions.{what}: slot {slot} is not open")
+
+    def feed(self, slot, mel):
+        self._live(slot, "feed")
+        C = self.vocoder.model.in_channels
+        if self._closing[slot]:
+            raise ValueError(f"VocoderSessions.feed: slot {slot} is closing")
+        if mel.dim() != 2 or mel.shape[1] != C:
+            raise ValueError(f"VocoderSessions.feed: expected (n, {C}), got {tuple(mel.shape)}")
+        if mel.shape[0]:
+            self._queue[slot].append(mel.detach())
+
+    def queued(self, slot):
+        """frames of `slot` waiting for a step()"""
+        self._live(slot, "queued")
+        return sum(m.shape[0] for m in self._queue[slot])
+
+    def close(self, slot):
+        """no more frames for `slot`: it is freed at once if its queue is empty, else by the step() that drains it"""
+        self._live(slot, "close")
+        self._closing[slot] = True
+        self._release()
+
+    def _release(self):
+        for slot, q in enumerate(self._queue):
+            if q is not None and self._closing[slot] and not q:
+                self._queue[slot], self._closing[slot] = None, False
+
+    def _take(self, slot):
+        """up to chunk_frames frames from the front of the slot's queue, as one (n, 80) tensor or None"""
+        q, got, n = self._queue[slot], [], 0
+        while q and n < self.chunk_frames:
+            m = q.pop(0)
+            room = self.chunk_frames - n
+            if m.shape[0] > room:
+                q.insert(0, m[room:])
+                m = m[:room]
+            got.append(m)
+            n += m.shape[0]
+        return torch.cat(got) if got else None
+
+    def step(self):
+        taken = {slot: self._take(slot) for slot, q in enumerate(self._queue) if q is not None}
+        lens = [0 if taken.get(b) is None else taken[b].shape[0] for b in range(self.slots)]
+        if max(lens) == 0:
+            return {}
+        c = torch.zeros(self.slots, max(lens), self.vocoder.model.in_channels, device=self.vocoder.device)
+        for b, m in taken.items():
+            if m is not None:
+                c[b, :m.shape[0]].copy_(m)
+        restart = [self._fresh[b] and b in taken for b in range(self.slots)]
+        y = self.stream.push(c, lens, restart)
+        hop = self.vocoder.model.hop
+        for b in taken:
+            self._fresh[b] = False
+        self._release()
+        return {b: y[b, :lens[b] * hop].clone() for b in taken if lens[b]}
